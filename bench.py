@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — BPR training triplets/sec on MI355X (BASELINE.json metric), one process per GPU.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 N=1 workload = BASELINE.json configs[1]: BPRMF, emb_size=64, synthetic 1M users x 1M items (uniform ids from the
 100M-interaction generator, seed 3407), batch 65,536 triplets, SGD, l2=0.  A "step" is one BaseRunner.fit iteration
@@ -15,8 +15,11 @@ N>1 (`python bench.py --gpus N` starts its own N ranks; under `torch.distributed
 tables row-sharded over N GPUs, RCCL over xGMI, both sharding modes in one run (see whisprrec_amd/rotating.py and
 whisprrec_amd/sharded.py); `--emb 128 --users 10000000 --items 10000000` is BASELINE.json configs[3].
 
-Prints ONE JSON line (rank 0).  `roofline` prices the dominant kernel against the 8 TB/s HBM peak using
-algorithmic bytes; `cpu_baseline` times the oracle's sparse SGD restatement on one host core.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and prints the headline (`value`,
+`ms_per_step`); `roofline` is null.  `--full` adds everything else, each in runs of its own after the timed steps:
+`roofline` prices the dominant kernel against the 8 TB/s HBM peak using algorithmic bytes from a per-kernel
+timing pass; `extra` holds the Adam and whole-epoch figures (N=1); `cpu_baseline` times the oracle's sparse SGD
+restatement on one host core.  `--dump-outputs DIR` (N=1) writes what the timed steps handed back, as .npy files.
 """
 import argparse
 import hashlib
@@ -53,10 +56,16 @@ def parse(argv=None):
     ap.add_argument("--plan-stream", choices=["side", "inline"], default="side",
                     help="N=1: where the next chunk's plan is built: on a side stream beside the steps (default), or on the "
                          "step stream between the halves of the current chunk (measured slower; kept for the A/B)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline, also run the per-kernel timing pass (roofline), the Adam and whole-epoch figures "
+                         "(N=1) and the CPU baselines; the --no-* options below drop single parts of it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="N=1: after the timed steps, write their losses and a fixed sample of rows of both updated tables to "
+                         "DIR/*.npy (float32 / float64)")
     ap.add_argument("--no-adam", action="store_true",
-                    help="N=1: skip the Adam figure reported under `extra` (the reference's default optimizer on the same shape)")
+                    help="N=1, --full: skip the Adam figure reported under `extra` (the reference's default optimizer on the same shape)")
     ap.add_argument("--no-epoch", action="store_true",
-                    help="N=1: skip the whole-epoch figure reported under `extra` (negative sampling + shuffle + plans + steps)")
+                    help="N=1, --full: skip the whole-epoch figure reported under `extra` (negative sampling + shuffle + plans + steps)")
     ap.add_argument("--epoch-interactions", type=int, default=100_000_000,
                     help="N=1: interactions of the synthetic training frame of the whole-epoch figure")
     ap.add_argument("--no-group", action="store_true",
@@ -269,11 +278,14 @@ def single_gpu(args, local_rank):
     plan = handle["cur"][1]            # the plan of the last timed chunk: the per-kernel timing pass runs on it
     tabs = handle["segs"][0]["tabs"]
     grouped = isinstance(plan, hip_ops.GroupPlan)
-    # per-kernel timing: HIP events that the library attaches to the dispatches of the step kernels (the kernels' own start /
-    # end timestamps), on a second pass over already planned batches — outside the throughput measurement, so nothing extra
-    # sits in the timed region.
+    if args.dump_outputs:
+        tabs.check_chain()
+        dump_outputs(args.dump_outputs, losses, U, I, u, p, n, (W + K - 1) * B, B)
+    # per-kernel timing (--full): HIP events that the library attaches to the dispatches of the step kernels (the kernels' own
+    # start / end timestamps), on a second pass over already planned batches — outside the throughput measurement, so nothing
+    # extra sits in the timed region.
     events, KP, chain_ev, chained, group_ev = None, 0, None, [], None
-    if not args.no_phase_events:
+    if args.full and not args.no_phase_events:
         KP = min(K, 64, plan.n_batches)
 
         def fresh_events(per_step=4):
@@ -312,28 +324,28 @@ def single_gpu(args, local_rank):
     assert np.all(np.isfinite(lv)), "non-finite loss"
     value = K * B / dt
 
-    # unique rows per step (for algorithmic bytes with in-batch duplicates counted once): from the ids of up
-    # to 8 batches of the last timed chunk
-    lo_p = handle["cur"][0] * B
-    nbs = max(1, min(8, plan.n_triplets // B))
-    uniq_u = uniq_i = single_i = 0.0
-    for k in range(nbs):
-        sl = slice(lo_p + k * B, lo_p + (k + 1) * B)
-        uniq_u += torch.unique(u[sl]).numel() / nbs
-        _, ci = torch.unique(torch.cat([p[sl], n[sl]]), return_counts=True)
-        uniq_i += ci.numel() / nbs
-        single_i += int((ci == 1).sum().item()) / nbs
-    row = D * 4
-    # Algorithmic bytes: every unique row of the batch read once and written once + 12 B of indices
-    # per triplet.  Split by who does it in the two-launch form: the user phase reads all of them, writes the user rows and
-    # the single-occurrence item rows; the item phase writes the item rows that have several occurrences (its re-read of
-    # those rows and the stash traffic are overhead, not algorithmic).
-    bytes_user = row * (2 * uniq_u + uniq_i + single_i) + 12 * B
-    bytes_item = row * (uniq_i - single_i)
-    bytes_step = bytes_user + bytes_item
-
     roofline = None
     if events is not None:
+        # unique rows per step (for algorithmic bytes with in-batch duplicates counted once): from the ids of
+        # up to 8 batches of the last timed chunk
+        lo_p = handle["cur"][0] * B
+        nbs = max(1, min(8, plan.n_triplets // B))
+        uniq_u = uniq_i = single_i = 0.0
+        for k in range(nbs):
+            sl = slice(lo_p + k * B, lo_p + (k + 1) * B)
+            uniq_u += torch.unique(u[sl]).numel() / nbs
+            _, ci = torch.unique(torch.cat([p[sl], n[sl]]), return_counts=True)
+            uniq_i += ci.numel() / nbs
+            single_i += int((ci == 1).sum().item()) / nbs
+        row = D * 4
+        # Algorithmic bytes: every unique row of the batch read once and written once + 12 B of indices
+        # per triplet.  Split by who does it in the two-launch form: the user phase reads all of them, writes the user rows
+        # and the single-occurrence item rows; the item phase writes the item rows that have several occurrences (its re-read
+        # of those rows and the stash traffic are overhead, not algorithmic).
+        bytes_user = row * (2 * uniq_u + uniq_i + single_i) + 12 * B
+        bytes_item = row * (uniq_i - single_i)
+        bytes_step = bytes_user + bytes_item
+
         t_user = np.mean([events[4 * k].elapsed_time(events[4 * k + 1]) for k in range(KP)]) * 1e-3
         t_item = np.mean([events[4 * k + 2].elapsed_time(events[4 * k + 3]) for k in range(KP)]) * 1e-3
         if t_item >= t_user:
@@ -396,16 +408,45 @@ def single_gpu(args, local_rank):
                       "host_queue_ms_of_timed_region": host_queue_ms},
            "loss_first": float(lv[0]), "loss_last": float(lv[-1]),
            "roofline": roofline}
-    if not args.no_adam:
+    if args.full and not args.no_adam:
         out["extra"] = {"adam": adam_extra(args, hip_ops, U, I, u, p, n, dev)}
-    if not args.no_epoch:
+    if args.full and not args.no_epoch:
         del u, p, n
         out.setdefault("extra", {})["epoch"] = epoch_extra(args, hip_ops, U, I, dev)
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args, args.cpu_seconds)
         out["cpu_baseline_torch"] = cpu_torch_sequence(args, max(4.0, args.cpu_seconds / 2))
     print(json.dumps(out))
     return 0
+
+
+DUMP_TRIPLETS = 8192          # --dump-outputs: rows of the first triplets of the last timed batch ...
+DUMP_RANDOM_ROWS = 8192       # ... and this many seeded rows of each table
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(out_dir, losses, U, I, u, p, n, last, B):
+    """What the timed steps hand back to their caller: the loss of every timed step (losses.npy; the last step's is the last
+    entry) and the two tables as the last timed step left them.  The tables are far larger than a dump may be (2 x 256 MB at
+    the default shape), so a fixed sample of their rows is written, ids ascending: the rows that the first DUMP_TRIPLETS
+    triplets of the last timed batch (stream offset `last`) updated, and DUMP_RANDOM_ROWS rows of each table drawn with a fixed
+    seed.  user_rows.npy / item_rows.npy [rows, D] float32, user_ids.npy / item_ids.npy float64."""
+    import numpy as np
+    import torch
+    rng = np.random.RandomState(3407)
+    sl = slice(last, last + min(B, DUMP_TRIPLETS))
+    arrays = {"losses": losses.cpu().numpy().astype(np.float32)}
+    for name, tab, cols in (("user", U, [u[sl]]), ("item", I, [p[sl], n[sl]])):
+        touched = torch.cat(cols).cpu().numpy().astype(np.int64)
+        ids = np.union1d(touched, rng.randint(0, tab.shape[0], DUMP_RANDOM_ROWS))
+        ids = ids[:max(1, (DUMP_LIMIT_BYTES // 3) // (tab.shape[1] * 4 + 8))]   # each table within a third of the limit
+        rows = tab.index_select(0, torch.from_numpy(ids).to(tab.device)).cpu().numpy()
+        arrays[name + "_ids"] = ids.astype(np.float64)
+        arrays[name + "_rows"] = rows.astype(np.float32)
+    os.makedirs(out_dir, exist_ok=True)
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_LIMIT_BYTES
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
 
 
 def adam_extra(args, hip_ops, U, I, u, p, n, dev):
@@ -524,7 +565,7 @@ def multi_gpu(args, rank, world, local_rank):
         torch.cuda.synchronize()
         dist.barrier()
     cpu = None
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline(args, min(args.cpu_seconds, 8.0))
     if rank == 0:
         emit(multi_line(args, world, results, cpu))
@@ -562,6 +603,8 @@ def multi_line(args, world, results, cpu, dry_run=False):
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     args = parse(argv)
+    if args.dump_outputs and (args.gpus > 1 or args.force_sharded):
+        raise SystemExit("bench.py --dump-outputs: single-GPU runs only")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus > 1 and "RANK" not in os.environ:
         return launch_ranks(args, argv)          # plain `python bench.py --gpus N`: start the N ranks ourselves

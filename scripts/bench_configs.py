@@ -240,7 +240,8 @@ def ml100k_dropin_case():
     import argparse as ap
     from whisprrec_amd.bprmf import BPRMF
     from whisprrec_amd import runner
-    g2 = np.load(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "g2_ml100k_curve.npz"))
+    import oracle
+    g2 = oracle.load_golden("g2_ml100k_curve")
     ptr, idx = g2["clicked_ptr"], g2["clicked_idx"]
     tcs = {u: set(idx[ptr[u]:ptr[u + 1]].tolist()) for u in range(943)}
     data = {"train": {"user_id": g2["train_user"].astype(np.int64), "item_id": g2["train_item"].astype(np.int64)},

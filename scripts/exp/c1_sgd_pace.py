@@ -6,7 +6,8 @@ import numpy as np, torch
 from whisprrec_amd import host, runner
 from whisprrec_amd.bprmf import BPRMF
 dev = torch.device("cuda:0")
-g2 = np.load(os.path.join(ROOT, "tests", "golden", "g2_ml100k_curve.npz"))
+import oracle
+g2 = oracle.load_golden("g2_ml100k_curve")
 ptr, idx = g2["clicked_ptr"], g2["clicked_idx"]
 tcs = {u: set(idx[ptr[u]:ptr[u + 1]].tolist()) for u in range(943)}
 data = {"train": {"user_id": g2["train_user"].astype(np.int64), "item_id": g2["train_item"].astype(np.int64)},

@@ -8,15 +8,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-GOLDEN = os.path.join(ROOT, "tests", "golden")
+from oracle import GOLDEN, load_golden  # noqa: E402  (one loader for tests and scripts: merges sets written in parts)
 
 
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (run with -m gpu on the GPU box)")
-
-
-def load_golden(name):
-    return np.load(os.path.join(GOLDEN, name + ".npz"))
 
 
 def rel_err(a, b):

@@ -24,6 +24,9 @@ Reference entry points exercised (paths relative to /root/reference):
       SGL.py:148-246 (three propagations, sum-BPR + EmbLoss + InfoNCE, grads), per view type ED / ND / RW
 """
 import argparse
+import glob
+import gzip
+import io
 import os
 import shutil
 import sys
@@ -64,10 +67,46 @@ def _args(**kw):
     return argparse.Namespace(**base)
 
 
+PART_BYTES = 960 * 1024    # a committed file stays under 1 MiB
+FILE_LIMIT = 1 << 20
+
+
+def _npz_bytes(arrays):
+    buf = io.BytesIO()
+    np.savez_compressed(buf, **arrays)
+    return len(buf.getvalue())
+
+
 def save(name, **arrays):
-    path = os.path.join(HERE, name + ".npz")
-    np.savez_compressed(path, **arrays)
-    print("wrote", path, {k: (v.shape, str(v.dtype)) for k, v in arrays.items() if hasattr(v, "shape")})
+    """name.npz; a set whose compressed arrays add up to more than PART_BYTES goes out as name.npz + name.part1.npz +
+    name.part2.npz ..., arrays in order (oracle.load_golden merges them back)"""
+    for old in glob.glob(os.path.join(HERE, name + ".part*.npz")):
+        os.remove(old)
+    parts, cur, size = [], {}, 0
+    for k, v in arrays.items():
+        nb = _npz_bytes({k: v})
+        if cur and size + nb > PART_BYTES:
+            parts.append(cur)
+            cur, size = {}, 0
+        cur[k] = v
+        size += nb
+    parts.append(cur)
+    for i, part in enumerate(parts):
+        path = os.path.join(HERE, name + (".part%d" % i if i else "") + ".npz")
+        np.savez_compressed(path, **part)
+        assert os.path.getsize(path) <= FILE_LIMIT, "%s: one array alone is larger than a committed file may be" % path
+        print("wrote", path, {k: (v.shape, str(v.dtype)) for k, v in part.items() if hasattr(v, "shape")})
+
+
+def ml100k_inter():
+    """the reference's ml-100k.inter, gzipped byte for byte (header and row order kept) for tests/test_reader.py"""
+    src = os.path.join(REF, "data", "ml-100k", "ml-100k.inter")
+    path = os.path.join(HERE, "ml-100k.inter.gz")
+    with open(src, "rb") as f, open(path, "wb") as raw:
+        with gzip.GzipFile(filename="", mode="wb", fileobj=raw, compresslevel=9, mtime=0) as gz:
+            gz.write(f.read())
+    assert os.path.getsize(path) <= FILE_LIMIT
+    print("wrote", path)
 
 
 # --------------------------------------------------------------------------------------------- G1
@@ -533,8 +572,9 @@ def g9_end_to_end():
 
 
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g6", "g7", "g8", "g9"]
+    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g6", "g7", "g8", "g9", "inter"]
     torch.set_num_threads(4)
     for w in which:
         {"g1": g1_bprmf_step, "g2": g2_ml100k_curve, "g3": g3_sampler, "g4": g4_lightgcn,
-         "g5": g5_sasrec_emb, "g6": g6_eval, "g7": g7_sgl, "g8": g8_reader, "g9": g9_end_to_end}[w]()
+         "g5": g5_sasrec_emb, "g6": g6_eval, "g7": g7_sgl, "g8": g8_reader, "g9": g9_end_to_end,
+         "inter": ml100k_inter}[w]()

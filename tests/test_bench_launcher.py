@@ -7,7 +7,10 @@ import os
 import subprocess
 import sys
 
-from conftest import ROOT
+import numpy as np
+import pytest
+
+from conftest import ROOT, rel_err
 
 import bench
 
@@ -70,3 +73,70 @@ def test_plan_chunk_of_a_short_run_is_the_run():
     assert bench.plan_chunk(bench.parse(["--steps", "20", "--warmup", "5"])) == 20
     assert bench.plan_chunk(bench.parse([])) == 64
     assert bench.plan_chunk(bench.parse(["--steps", "20", "--chunk", "7"])) == 7
+
+
+def test_full_and_dump_outputs_are_off_by_default():
+    args = bench.parse(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert not args.full and args.dump_outputs is None
+    assert bench.parse(["--full"]).full
+
+
+def test_dump_outputs_is_refused_off_the_single_gpu_path(tmp_path):
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-run", "--backend", "gloo",
+                        "--dump-outputs", str(tmp_path / "out")], env=env, capture_output=True, text=True, timeout=120)
+    assert r.returncode != 0 and "--dump-outputs" in (r.stdout + r.stderr) and not (tmp_path / "out").exists()
+
+
+@pytest.mark.gpu
+def test_plain_run_dumps_what_its_timed_steps_computed(tmp_path):
+    """a plain one-GPU run prints the headline without the --full parts, and --dump-outputs writes the same arrays (float32 /
+    float64, within 64 MB) from run to run: the timed steps' losses and a fixed sample of rows of both tables"""
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2", "--batch", "16384",
+           "--users", "300000", "--items", "300000"]
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
+    lines = []
+    for k in range(2):
+        r = subprocess.run(cmd + ["--dump-outputs", str(tmp_path / str(k))], env=env, capture_output=True, text=True,
+                           timeout=300)
+        assert r.returncode == 0, r.stdout + r.stderr
+        lines.append(_last_json(r.stdout))
+    line = lines[0]
+    assert line["steps"] == 6 and line["warmup"] == 2 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["roofline"] is None and "extra" not in line and "cpu_baseline" not in line
+    names = {"losses", "user_ids", "user_rows", "item_ids", "item_rows"}
+    assert {f[:-len(".npy")] for f in os.listdir(tmp_path / "0")} == names
+    got = {nm: [np.load(tmp_path / str(k) / (nm + ".npy")) for k in range(2)] for nm in names}
+    assert sum(a[0].nbytes for a in got.values()) <= 64e6
+    for nm, (a, b) in got.items():
+        assert a.dtype in (np.float32, np.float64) and a.shape == b.shape, nm
+    assert got["losses"][0].shape == (6,) and float(got["losses"][0][-1]) == line["loss_last"]
+    for nm in ("user", "item"):
+        ids, rows = got[nm + "_ids"][0], got[nm + "_rows"][0]
+        assert np.array_equal(ids, got[nm + "_ids"][1]) and np.all(np.diff(ids) > 0) and rows.shape == (ids.size, 64)
+        assert rel_err(rows, got[nm + "_rows"][1]) < 1e-6
+    assert rel_err(got["losses"][0], got["losses"][1]) < 1e-6
+
+    # the rows are the trained tables' and line up with their ids: with the tables and the triplet stream rebuilt here as
+    # bench.single_gpu seeds them, a sampled row that no warm-up or timed step touched still holds its initial value, every
+    # row of the last batch's dumped triplets is there, and those rows moved
+    import torch
+    args = bench.parse(cmd[2:])
+    dev = torch.device("cuda:0")
+    B, D, K, W = args.batch, args.emb, args.steps, args.warmup
+    g = torch.Generator(device=dev)
+    g.manual_seed(3407)
+    U0 = torch.randn(args.users, D, generator=g, device=dev) * float(np.sqrt(2.0 / (args.users + D)))
+    I0 = torch.randn(args.items, D, generator=g, device=dev) * float(np.sqrt(2.0 / (args.items + D)))
+    u, p, n = bench.synth_triplets((K + W + bench.plan_chunk(args)) * B, args.users, args.items, dev, 3407, args.zipf)
+    trained = slice(0, (W + K) * B)
+    last = slice((W + K - 1) * B, (W + K - 1) * B + min(B, bench.DUMP_TRIPLETS))
+    for nm, T0, cols in (("user", U0, (u,)), ("item", I0, (p, n))):
+        ids, rows = got[nm + "_ids"][0].astype(np.int64), got[nm + "_rows"][0]
+        init = T0[torch.from_numpy(ids).to(dev)].cpu().numpy()
+        touched = np.isin(ids, torch.cat([c[trained] for c in cols]).cpu().numpy())
+        last_ids = np.unique(torch.cat([c[last] for c in cols]).cpu().numpy())
+        in_last = np.isin(ids, last_ids)
+        assert in_last.sum() == last_ids.size, nm
+        assert (~touched).sum() > 1000 and np.array_equal(rows[~touched], init[~touched]), nm
+        assert np.mean(np.any(rows[in_last] != init[in_last], axis=1)) > 0.99, nm

@@ -52,14 +52,17 @@ def test_split_restatement_equals_sklearn():
         assert np.array_equal(tr, a) and np.array_equal(dv, d) and np.array_equal(te, t)
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/data/ml-100k/ml-100k.inter"), reason="reference data not on this machine")
-def test_full_ml100k_matches_the_training_golden(tmp_path):
-    """the whole file: the train split must be the one the reference trained on in tests/golden/g2_ml100k_curve.npz"""
+def test_full_ml100k_matches_the_training_golden(tmp_path, g2):
+    """the whole file (tests/golden/ml-100k.inter.gz, byte for byte): the train split must be the one the reference trained on
+    in tests/golden/g2_ml100k_curve.npz"""
+    import gzip
     import shutil
     from whisprrec_amd.reader import BaseReader
-    shutil.copytree("/root/reference/data/ml-100k", tmp_path / "ml-100k")
+    (tmp_path / "ml-100k").mkdir()
+    with gzip.open(os.path.join(os.path.dirname(__file__), "golden", "ml-100k.inter.gz"), "rb") as src, \
+            open(tmp_path / "ml-100k" / "ml-100k.inter", "wb") as dst:
+        shutil.copyfileobj(src, dst)
     r = BaseReader(argparse.Namespace(sep="\t", path=str(tmp_path) + "/", dataset="ml-100k", sample="random"))
-    g2 = np.load(os.path.join(os.path.dirname(__file__), "golden", "g2_ml100k_curve.npz"))
     assert (r.n_users, r.n_items) == (943, 1574) and r.all_df["user_id"].size == 82520
     assert np.array_equal(r.data_df["train"]["user_id"], g2["train_user"])
     assert np.array_equal(r.data_df["train"]["item_id"], g2["train_item"])
