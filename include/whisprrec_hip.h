@@ -727,6 +727,31 @@ int32_t wr_rank_eval(const float *user_mat, int64_t n_user_rows, const float *it
                      const int64_t *eval_user, const int64_t *eval_target, int64_t n, const int64_t *mask_ptr,
                      const int32_t *mask_idx, int32_t *rank, float *target_score, void *stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * K11  Top-K recommendation: for each query row q, the k unmasked items with the largest
+ *   score(q, j) = <user_mat[query_user[q]], item_tab[j]>, ordered by score descending, ties by item id ascending.
+ * The reference's save_rec_results (src/main.py:83-102, commented out there) over full_predict, without the [n, n_items]
+ * score matrix.
+ *   - Scores: the fp32 k-ordered chain of v_mfma_f32_32x32x2_f32 over k = 0..D-1 that wr_rank_eval computes: a returned
+ *     score is bitwise equal to wr_rank_eval's target_score for that (user, item) pair.
+ *   - Masking: mask_ptr int64 [n_user_rows+1] / mask_idx int32, ascending per user, as for wr_rank_eval; both NULL = no
+ *     mask.  A masked item is never returned.
+ *   - Order: score descending, then item id ascending (a stable descending sort).
+ *   - Padding: a row with fewer than k unmasked items ends with out_item = -1, out_score = -inf.
+ *   - out_item int32 [n, k], out_score fp32 [n, k], row-major.  1 <= k <= 256; D in {8, 16, 32, 64} (A operand in
+ *     registers) or a multiple of 4 up to 252 (A operand in LDS) — the set wr_rank_eval takes (wr_topk_supported).
+ *   - workspace >= wr_topk_workspace_bytes(n, n_items, D, k) bytes, 16-byte aligned; that bound never decreases as n,
+ *     n_items or k grow.  Argument errors (WR_E_*) are reported before anything is launched.
+ *   - Bitwise reproducible (no float atomics); no host round trip: capturable into a hipGraph.
+ * Two launches: a scoring kernel per (128 query rows, item chunk) that keeps each row's K best keys in the workspace, then a
+ * merge of the chunk lists per row. */
+int32_t wr_topk_supported(int32_t D, int32_t k);
+int64_t wr_topk_workspace_bytes(int64_t n, int64_t n_items, int32_t D, int32_t k);
+int32_t wr_topk_recommend(const float *user_mat, int64_t n_user_rows, const float *item_tab, int64_t n_items, int32_t D,
+                          const int64_t *query_user, int64_t n, const int64_t *mask_ptr, const int32_t *mask_idx,
+                          int32_t k, int32_t *out_item, float *out_score, void *workspace, int64_t workspace_bytes,
+                          void *stream);
+
 /* LightGCN.predict's per-batch tail in two launches (src/models/general/LightGCN.py:156-175, src/utils/loss.py:37-39,94-98):
  *   loss[0] = mean_b( -log(1e-10 + sigmoid(<Ua[u_b], Ia[p_b]> - <Ua[u_b], Ia[n_b]>)) )
  *             + reg_weight * (||U0[u]||_F + ||I0[p]||_F + ||I0[n]||_F) / B

@@ -1128,6 +1128,54 @@ def rank_eval(user_mat, item_tab, eval_user, eval_target, mask_ptr=None, mask_id
     return rank, tsc
 
 
+TOPK_MAX_K = 256
+TOPK_WORKSPACE_CAP = 2 << 30        # bytes of workspace per call at most: the users go in blocks below it
+
+
+def topk_supports(D, k):
+    """(D, k) that wr_topk_recommend takes: 1 <= k <= 256 and the embedding sizes of rank_eval_supports"""
+    return bool(abi.lib().wr_topk_supported(int(D), int(k)))
+
+
+def topk_recommend(user_mat, item_tab, users, k, mask_ptr=None, mask_idx=None):
+    """The k unmasked items with the largest <user_mat[u], item_tab[j]> for every u in `users`, by score descending, then
+    item id ascending (wr_topk_recommend).  Scores are bitwise those rank_eval computes.  Rows with fewer than k unmasked
+    items end with item -1 / score -inf.  Returns (items int64 [n, k], scores float32 [n, k]) on the device."""
+    _req(user_mat, torch.float32, "user_mat", 2)
+    _req(item_tab, torch.float32, "item_tab", 2)
+    qu = _idx64(users.reshape(-1), "users")
+    if (mask_ptr is None) != (mask_idx is None):
+        raise ValueError("mask_ptr and mask_idx go together")
+    if mask_ptr is not None:
+        _req(mask_ptr, torch.int64, "mask_ptr", 1)
+        _req(mask_idx, torch.int32, "mask_idx", 1)
+    k, D = int(k), int(user_mat.shape[1])
+    if item_tab.shape[1] != D:
+        raise ValueError("user_mat and item_tab have different widths (%d, %d)" % (D, item_tab.shape[1]))
+    if not topk_supports(D, k):
+        raise abi.WhisprRecHipError("topk_recommend does not support D=%d, k=%d (1 <= k <= %d; D as for rank_eval)"
+                                    % (D, k, TOPK_MAX_K))
+    L, dev = abi.lib(), user_mat.device
+    n, n_items = qu.numel(), item_tab.shape[0]
+    items = torch.empty((n, k), dtype=torch.int32, device=dev)
+    scores = torch.empty((n, k), dtype=torch.float32, device=dev)
+    # users in blocks whose workspace stays under the cap (the bound never decreases in n: halve until it fits)
+    block = max(n, 1)
+    while block > 128 and abi.check_size(L.wr_topk_workspace_bytes(block, n_items, D, k), "wr_topk_workspace_bytes") \
+            > TOPK_WORKSPACE_CAP:
+        block = (block + 1) // 2
+    ws = workspace(dev, "topk")
+    for lo in range(0, n, block):
+        hi = min(n, lo + block)
+        nb = abi.check_size(L.wr_topk_workspace_bytes(hi - lo, n_items, D, k), "wr_topk_workspace_bytes")
+        buf = ws.get(nb)
+        abi.check(L.wr_topk_recommend(_p(user_mat), user_mat.shape[0], _p(item_tab), n_items, D, _p(qu[lo:hi]), hi - lo,
+                                      _p(mask_ptr), _p(mask_idx), k, _p(items[lo:hi]), _p(scores[lo:hi]), _p(buf),
+                                      buf.numel(), _stream()),
+                  "wr_topk_recommend")
+    return items.to(torch.int64), scores
+
+
 # ----------------------------------------------------------------------------------------------- optimizers
 def sgd_dense(tab, grad, lr, l2=0.0, stamp=None, step_id=0):
     abi.check(abi.lib().wr_sgd_dense(_p(_req(tab, torch.float32, "tab", 2)), tab.shape[0], tab.shape[1],

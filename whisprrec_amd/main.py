@@ -68,6 +68,7 @@ def build_args(argv=None):
         args.log_file = "../log/{}/{}.txt".format(init_args.model_name, name)
     if args.model_path == "":
         args.model_path = "../model/{}/{}.pt".format(init_args.model_name, name)
+    args.model_name = init_args.model_name
     return args, model_class, reader_class, runner_class
 
 
@@ -94,6 +95,15 @@ def main(argv=None):
         run.train(data_dict)
     res = run.print_res(data_dict["test"])
     logging.info(os.linesep + "Test After Training: " + res)
+    save_rec = int(getattr(args, "save_rec", 0))
+    if save_rec > 0 and hasattr(run, "save_rec_results"):
+        rec_path = os.path.join(args.path, args.dataset, "rec-{}.csv".format(args.model_name))   # reference main.py:83,89
+        run.save_rec_results(data_dict["dev"], save_rec, rec_path, sep=getattr(args, "sep", "\t"))
+        logging.info("Saved top-{} recommendations of the dev rows to {}".format(save_rec, rec_path))
+    elif not hasattr(run, "save_rec_results") and any(a == "--save_rec" or a.startswith("--save_rec=")
+                                                      for a in (sys.argv[1:] if argv is None else argv)):
+        logging.warning("--save_rec is ignored: %s cannot write recommendations (use --runner_name HipRunner)",
+                        type(run).__name__)
     model.actions_after_train()
     return res
 

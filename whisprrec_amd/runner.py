@@ -255,6 +255,19 @@ class BaseRunner(object):
         return "(" + format_metric(self.evaluate(dataset, self.topk, self.metrics)) + ")"
 
 
+def write_rec_csv(path, users, rec_items, sep="\t"):
+    """user_id<sep>rec_items, then one line per row: the user and the Python list of its items — what
+    pandas.DataFrame({"user_id": users, "rec_items": lists}).to_csv(path, sep=sep, index=False) writes (the reference's
+    save_rec_results), through the csv module (QUOTE_MINIMAL: a list is quoted when sep is ',')."""
+    import csv
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f, delimiter=sep, quoting=csv.QUOTE_MINIMAL, lineterminator="\n")
+        w.writerow(["user_id", "rec_items"])
+        for u, row in zip(users, rec_items):
+            w.writerow([int(u), repr([int(x) for x in row])])
+    return path
+
+
 def _metrics_from_ranks(gt_rank, topk, metrics):
     return BaseRunner.metrics_from_ranks(gt_rank, topk, metrics)
 
@@ -270,6 +283,9 @@ def make_hip_runner(base_runner_cls):
                                      "as the reference sampler but not its NumPy stream). 0: reference streams, bit-exact.")
             parser.add_argument("--hip_graphs", type=int, default=1,
                                 help="1: capture the training step of graph-capturable models (LightGCN) in a hipGraph.")
+            parser.add_argument("--save_rec", type=int, default=0,
+                                help="K > 0: after training, write the K best items of every dev row to "
+                                     "<path>/<dataset>/rec-<model_name>.csv.")
             return base_runner_cls.parse_runner_args(parser)
 
         def __init__(self, args):
@@ -321,20 +337,73 @@ def make_hip_runner(base_runner_cls):
             model.eval()
             user_mat, item_mat = model.eval_factors()
             dev = user_mat.device
-            cache = getattr(self, "_mask_cache", None)
-            if cache is None or cache[0] is not dataset.corpus or cache[1] != bool(model.test_all):
-                if model.test_all:
-                    corpus = dataset.corpus
-                    merged = {u: corpus.train_clicked_set.get(u, set()) | corpus.residual_clicked_set.get(u, set())
-                              for u in set(corpus.train_clicked_set) | set(corpus.residual_clicked_set)}
-                    ptr, idx = hip_ops.clicked_csr(merged, user_mat.shape[0], dev)
-                else:
-                    ptr = idx = None
-                cache = self._mask_cache = (dataset.corpus, bool(model.test_all), ptr, idx)
+            ptr, idx = self._clicked_mask(dataset.corpus, bool(model.test_all), user_mat.shape[0], dev)
             eu = torch.from_numpy(np.ascontiguousarray(dataset.data["user_id"])).to(dev)
             et = torch.from_numpy(np.ascontiguousarray(dataset.data["item_id"])).to(dev)
-            rank, _ = hip_ops.rank_eval(user_mat.contiguous(), item_mat.contiguous(), eu, et, cache[2], cache[3])
+            rank, _ = hip_ops.rank_eval(user_mat.contiguous(), item_mat.contiguous(), eu, et, ptr, idx)
             return self.metrics_from_ranks(rank.cpu().numpy().astype(np.int64), topks, metrics)
+
+        def _clicked_mask(self, corpus, test_all, n_user_rows, dev):
+            """device CSR of the items the full ranking sets to -inf (BaseRunner.py:246-255): each user's train + dev + test
+            items under --test_all 1, none (None, None) otherwise; built once per (corpus, test_all)"""
+            from . import hip_ops
+            cache = getattr(self, "_mask_cache", None)
+            if cache is None or cache[0] is not corpus or cache[1] != bool(test_all):
+                if test_all:
+                    merged = {u: corpus.train_clicked_set.get(u, set()) | corpus.residual_clicked_set.get(u, set())
+                              for u in set(corpus.train_clicked_set) | set(corpus.residual_clicked_set)}
+                    ptr, idx = hip_ops.clicked_csr(merged, n_user_rows, dev)
+                else:
+                    ptr = idx = None
+                cache = self._mask_cache = (corpus, bool(test_all), ptr, idx)
+            return cache[2], cache[3]
+
+        def recommend(self, model, corpus, users, k, exclude="clicked"):
+            """The k best items for every user id in `users` (wr_topk_recommend: MFMA score tiles with a selection stage, no
+            [n, n_items] score matrix), by score descending, then item id ascending.  Returns numpy (items int64 [n, k],
+            scores float32 [n, k]); a user with fewer than k items left ends with item -1 / score -inf.
+              exclude="clicked": the user's train + dev + test items are never recommended (the mask `evaluate` uses
+                                 under --test_all 1, from the same cache);
+              exclude="train":   only the training items (corpus.train_clicked_set);
+              exclude="none":    every item.
+            Needs a model whose scores are inner products of two factor matrices (``eval_factors``: BPRMF, LightGCN, SGL).
+            SASRec is out of scope: its query vector depends on each row's history, not on the user id alone."""
+            from . import hip_ops
+            if not hasattr(model, "eval_factors"):
+                raise NotImplementedError("%s has no eval_factors(): HipRunner.recommend needs a model whose scores are "
+                                          "inner products of a user and an item matrix" % type(model).__name__)
+            model.eval()
+            user_mat, item_mat = model.eval_factors()
+            D = user_mat.shape[1]
+            if not hip_ops.topk_supports(D, k):
+                raise NotImplementedError("%s: HipRunner.recommend does not support embedding size %d with k=%d"
+                                          % (type(model).__name__, D, k))
+            dev = user_mat.device
+            if exclude == "clicked":
+                ptr, idx = self._clicked_mask(corpus, True, user_mat.shape[0], dev)
+            elif exclude == "train":
+                cache = getattr(self, "_train_mask_cache", None)
+                if cache is None or cache[0] is not corpus:
+                    cache = self._train_mask_cache = (corpus,) + hip_ops.clicked_csr(corpus.train_clicked_set,
+                                                                                      user_mat.shape[0], dev)
+                ptr, idx = cache[1], cache[2]
+            elif exclude == "none":
+                ptr = idx = None
+            else:
+                raise ValueError("exclude must be 'clicked', 'train' or 'none' (got %r)" % (exclude,))
+            uq = torch.from_numpy(np.ascontiguousarray(np.asarray(users, dtype=np.int64).reshape(-1))).to(dev)
+            with torch.no_grad():
+                items, scores = hip_ops.topk_recommend(user_mat.contiguous(), item_mat.contiguous(), uq, k, ptr, idx)
+            return items.cpu().numpy(), scores.cpu().numpy()
+
+        def save_rec_results(self, dataset, k, path, sep="\t"):
+            """The reference's save_rec_results (src/main.py:83-102, commented out there): one line per row of `dataset`, in
+            order, with that row's user and its k best items, masked as `evaluate` masks them for this model (test_all)."""
+            model = dataset.model
+            users = np.asarray(dataset.data["user_id"], dtype=np.int64)
+            items, _ = self.recommend(model, dataset.corpus, users, k, exclude="clicked" if model.test_all else "none")
+            write_rec_csv(path, users, items, sep)
+            return path
 
         def _step_graph(self, model, cols, B, n, eager_step):
             """hipGraph of one whole training step (zero_grad / predict / backward / optimizer.step) of a model that declares
