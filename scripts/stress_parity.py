@@ -5,6 +5,7 @@ import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 import oracle
+from oracle import parity
 from whisprrec_amd import hip_ops
 
 dev = torch.device("cuda:0")
@@ -12,7 +13,7 @@ budget = float(sys.argv[1]) if len(sys.argv) > 1 else 60.0
 t_end = time.time() + budget
 t_note = time.time()
 rng = np.random.RandomState(int(sys.argv[2]) if len(sys.argv) > 2 else 0)
-n_cases = worst = n_mapped = 0
+n_cases = worst = worst_upd = worst_row = n_mapped = 0
 T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
 while time.time() < t_end:
     D = int(rng.choice([4, 8, 16, 20, 32, 64, 64, 64, 96, 128, 256]))
@@ -50,6 +51,10 @@ while time.time() < t_end:
     e = max(np.abs(res[0][0].cpu().numpy() - Uo).max() / max(np.abs(Uo).max(), 1e-30), np.abs(res[0][1].cpu().numpy() - Io).max() / max(np.abs(Io).max(), 1e-30))
     assert e < 2e-5, ("tables", D, nU, nI, B, kind, e)
     worst = max(worst, e)
+    # the same run against the float64 reference, error measured against the update (oracle/parity.py; reported, no threshold:
+    # at lr = 0.1 and these ids the update is not in the regime the tolerances of the test suite were derived for)
+    fig = parity.sgd_run_errors(U, I, parity.bprmf_sgd_f64(U, I, u, p, n, B, 0.1), res[0][0].cpu().numpy(), res[0][1].cpu().numpy())
+    worst_upd, worst_row = max(worst_upd, fig["update_err"]), max(worst_row, fig["row_update_err"])
     # lazy Adam (fused step) vs dense Adam, bitwise
     l2 = float(rng.choice([0.0, 1e-3]))
     Ud, Id = T(U), T(I); td = hip_ops.BprmfTables(Ud, Id); z = torch.zeros_like
@@ -96,4 +101,5 @@ while time.time() < t_end:
     if time.time() - t_note > 30:             # a run silent for minutes is taken to be hung on the GPU pool
         t_note = time.time()
         print("stress_parity: %d cases so far" % n_cases, flush=True)
-print("stress_parity: %d random cases ok (%d with the mapped bucket builder), worst table rel err %.2e" % (n_cases, n_mapped, worst))
+print("stress_parity: %d random cases ok (%d with the mapped bucket builder), worst table rel err %.2e; against float64: worst "
+      "update_err %.2e, worst row_update_err %.2e" % (n_cases, n_mapped, worst, worst_upd, worst_row))

@@ -1,7 +1,9 @@
 """GPU parity tests of the BPRMF hot path: HIP kernels (through the C-ABI) vs the golden vectors produced by the
 reference and vs the CPU oracle on seeded inputs.
 
-Bar (BASELINE.json north_star): indices bit-exact; fp32 embeddings / loss within 1e-5 relative.
+Bar (BASELINE.json north_star): indices bit-exact; fp32 embeddings / loss within 1e-5 relative.  The step tests against the
+oracle add a probe run (oracle/parity.py): the same batches from the same tables at parity.probe_lr(B) against the float64
+reference, with the error measured against the update, per table and per row.
 """
 import numpy as np
 import pytest
@@ -9,6 +11,7 @@ import torch
 
 import oracle
 from conftest import rel_err
+from oracle import parity
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-5
@@ -275,14 +278,24 @@ def test_step_vs_oracle_embedding_sizes(ops, dev, D):
     I = (rng.standard_normal((nI, D)) / np.sqrt(D) * 3).astype(np.float32)
     tabs = ops.BprmfTables(T(U, dev), T(I, dev))
     Uo, Io = U.copy(), I.copy()
+    ids = []
     for k in range(3):
         u, p, n = rng.randint(0, nU, B), rng.randint(0, nI, B), rng.randint(0, nI, B)
+        ids.append((u, p, n))
         plan = ops.BatchPlan(T(u, dev), T(p, dev), T(n, dev), B, nU, nI)
         loss = tabs.step_sgd(plan, 0, 0.2)
         lo = oracle.bprmf_step_sgd(Uo, Io, u, p, n, 0.2, 0.0)
         assert abs(float(loss) - lo) / lo < TOL
     assert rel_err(tabs.U.cpu().numpy(), Uo) < TOL
     assert rel_err(tabs.I.cpu().numpy(), Io) < TOL
+    # probe run: per row, which is where a wrong tail lane at D = 96 / 500 shows
+    tabs = ops.BprmfTables(T(U, dev), T(I, dev))
+    losses = []
+    for u, p, n in ids:
+        plan = ops.BatchPlan(T(u, dev), T(p, dev), T(n, dev), B, nU, nI)
+        losses.append(float(tabs.step_sgd(plan, 0, parity.probe_lr(B))))
+    u, p, n = (np.concatenate([b[j] for b in ids]) for j in range(3))
+    parity.check_sgd_run("step D%d" % D, U, I, u, p, n, B, parity.probe_lr(B), tabs.U, tabs.I, losses)
 
 
 def test_single_hot_row_and_untouched_rows(ops, dev):
@@ -379,6 +392,12 @@ def test_random_shapes_vs_oracle(ops, dev, case):
            for k in range((N + B - 1) // B)]
     assert rel_err(out[0][2], np.asarray(ref)) < TOL
     assert rel_err(out[0][0], Uo) < TOL and rel_err(out[0][1], Io) < TOL
+    if kind == 0:        # probe run on the uniform ids (clustered and power-law ids put thousands of occurrences of a batch on
+        tabs = ops.BprmfTables(T(U, dev), T(I, dev))          # a handful of rows: at probe_lr those rows leave the table's scale)
+        plan = ops.BatchPlan(T(u, dev), T(p, dev), T(n, dev), B, nU, nI)
+        lp = tabs.run_sgd(plan, 0, plan.n_batches, parity.probe_lr(B))
+        parity.check_sgd_run("random shape %d: %dx%d D%d B%d" % (case, nU, nI, D, B), U, I, u, p, n, B, parity.probe_lr(B),
+                             tabs.U, tabs.I, lp)
 
 
 @pytest.mark.parametrize("D", [64, 16])
@@ -460,6 +479,10 @@ def test_full_size_step_c2(ops, dev):
     tabs2 = ops.BprmfTables(Ud.clone(), Id.clone())
     tabs2.step_sgd(plan, 0, 0.05)
     assert torch.equal(tabs2.U, tabs.U) and torch.equal(tabs2.I, tabs.I)
+    probe = ops.BprmfTables(Ud.clone(), Id.clone())               # probe run: lr = 983
+    lp = probe.step_sgd(plan, 0, parity.probe_lr(B))
+    parity.check_sgd_run("full-size step 1Mx1M D64 B65536", U.numpy(), I.numpy(), u, p, n, B, parity.probe_lr(B), probe.U,
+                         probe.I, lp.reshape(1))
 
 
 @pytest.mark.parametrize("hot", [False, True])

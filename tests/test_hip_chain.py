@@ -4,13 +4,16 @@ the item workgroups add to after their write-through row stores.  Semantics are 
 (src/helpers/BaseRunner.py:194-200: strictly sequential, batch-synchronous steps), so the checks are: tables after N chained
 steps BIT-IDENTICAL to the two-launch stream's (a stale read of a handed-over row would break exactly that) and equal to the
 oracle's; losses equal to rounding and bitwise reproducible; steps with too many deferred runs, the first step of a call and
-plans that do not qualify take the two-launch form; no wait ever expires."""
+plans that do not qualify take the two-launch form; no wait ever expires.  Bit-identity with the two-launch stream says nothing
+if both read the same stale row, and at the tests' learning rates the 1e-5 bound on the table cannot fail: the probe runs
+(oracle/parity.py) repeat the chained run at parity.probe_lr(B) against the float64 reference, error measured against the update."""
 import numpy as np
 import pytest
 import torch
 
 import oracle
 from conftest import rel_err
+from oracle import parity
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-5
@@ -76,6 +79,12 @@ def test_chained_steps_equal_two_launch_steps_bitwise(ops, nI, D, B):
               for k in range(nb)]
     assert rel_err(outs[0][2].cpu().numpy(), np.asarray(lo_ref)) < TOL
     assert rel_err(outs[0][0].cpu().numpy(), Uo) < TOL and rel_err(outs[0][1].cpu().numpy(), Io) < TOL
+    tabs = ops.BprmfTables(T(U, dev), T(I, dev))                          # probe run, chained form
+    tabs.run_sgd_chain(plan, 0, 4, parity.probe_lr(B), losses[:4])
+    tabs.run_sgd_chain(plan, 4, nb - 4, parity.probe_lr(B), losses[4:])
+    torch.cuda.synchronize()
+    tabs.check_chain()
+    parity.check_sgd_run("chain 70Kx%d D%d B%d" % (nI, D, B), U, I, u, p, n, B, parity.probe_lr(B), tabs.U, tabs.I, losses)
 
 
 def test_mixed_chained_and_two_launch_steps(ops):
@@ -126,6 +135,13 @@ def test_headline_shape_many_steps(ops):
         assert rel_err(l_chain.cpu().numpy(), l_ref.cpu().numpy()) < 1e-6
     fwd = ops.bpr_fwd(U0, I0, u[:B].long(), p[:B].long(), n[:B].long(), scores=False)["loss"]
     assert abs(float(fwd) - float(l_ref[0])) < 1e-6 * abs(float(fwd))
+    del ref
+    tabs = ops.BprmfTables(U0.clone(), I0.clone())                  # probe run: 24 chained steps at lr = 983
+    l_chain = tabs.run_sgd_chain(plan, 0, nb, parity.probe_lr(B))
+    torch.cuda.synchronize()
+    tabs.check_chain()
+    parity.check_sgd_run("chain headline 1Mx1M D64 B65536, 24 steps", U0, I0, u, p, n, B, parity.probe_lr(B), tabs.U, tabs.I,
+                         l_chain)
 
 
 def test_chain_entry_refuses_rows_that_are_not_whole_lines(ops):
@@ -236,11 +252,21 @@ def test_c4_shape_chained(ops):
     arena = ops.PlanArena(dev, nb * B, B, overlap_items=nI)
     plan = ops.BatchPlan(u, p, n, B, nU, nI, arena=arena, overlap=True)
     assert plan.overlap is not None and plan._bitmap_ready                    # the builder wrote the bitmap itself (shift 16)
+    tu, ti = parity.touched_rows(u.cpu().numpy(), p.cpu().numpy(), n.cpu().numpy())
+    Uc, Ic = parity.take_rows(U0, tu), parity.take_rows(I0, ti)               # the touched rows before any run, for the probe run
     ref = ops.BprmfTables(U0.clone(), I0.clone())
     l_ref = ref.run_sgd(plan, 0, nb, lr)
-    tabs = ops.BprmfTables(U0, I0)
+    tabs = ops.BprmfTables(U0.clone(), I0.clone())
     l_chain = tabs.run_sgd_chain(plan, 0, nb, lr)
     torch.cuda.synchronize()
     tabs.check_chain()
     assert torch.equal(tabs.U, ref.U) and torch.equal(tabs.I, ref.I)
     assert rel_err(l_chain.cpu().numpy(), l_ref.cpu().numpy()) < 1e-6
+    del ref, tabs
+    torch.cuda.empty_cache()
+    tabs = ops.BprmfTables(U0, I0)                                            # probe run in place: lr = 983
+    l_chain = tabs.run_sgd_chain(plan, 0, nb, parity.probe_lr(B))
+    torch.cuda.synchronize()
+    tabs.check_chain()
+    parity.check_sgd_run("chain C4 10Mx10M D128 B65536", Uc, Ic, u, p, n, B, parity.probe_lr(B), parity.take_rows(tabs.U, tu),
+                         parity.take_rows(tabs.I, ti), l_chain, rows=(tu, ti))

@@ -4,7 +4,8 @@ tests stay below:
       power-law item popularity: the head items are rated by a large share of the users), B = 2,048: predict + backward
       against the oracle's restatement (reference src/models/general/LightGCN.py:134-175);
   C4  BPRMF emb_size=128 on 10M x 10M tables, B = 65,536 (one rank's batch of the 8-GPU configuration, here on one GPU):
-      one fused step against the oracle on the touched rows, every other row bit-identical, loss = the forward-only kernel's
+      one fused step against the oracle on the touched rows, every other row bit-identical, loss = the forward-only kernel's,
+      and a probe run of the sorted-plan step and of four group-plan steps against the float64 reference (oracle/parity.py)
       (reference src/models/general/BPRMF.py:69-80, src/helpers/BaseRunner.py:196-199);
   C5  SASRec's item-embedding slice at B = 2,048, history_max = 20, 3,706 items: gather bit-exact, scatter-add against the
       oracle, padding row 0 without gradient (reference src/models/sequential/SASRec.py:84,105-106).
@@ -17,6 +18,7 @@ import torch
 
 import oracle
 from conftest import rel_err
+from oracle import parity
 from whisprrec_amd import host
 
 pytestmark = pytest.mark.gpu
@@ -102,6 +104,7 @@ def test_c4_bprmf_d128_10m_tables_step_matches_oracle_on_touched_rows():
     ki, inv_i = np.unique(np.concatenate([p, n]), return_inverse=True)
     Uc = U0[torch.from_numpy(ku).to(dev)].cpu().numpy()
     Ic = I0[torch.from_numpy(ki).to(dev)].cpu().numpy()
+    Uc0, Ic0 = Uc.copy(), Ic.copy()
     loss_ref = oracle.bprmf_step_sgd(Uc, Ic, inv_u, inv_i[:B], inv_i[B:], lr, 0.0)
     assert abs(float(loss) - loss_ref) / loss_ref < TOL
     assert rel_err(tabs.U[torch.from_numpy(ku).to(dev)].cpu().numpy(), Uc) < TOL
@@ -114,9 +117,50 @@ def test_c4_bprmf_d128_10m_tables_step_matches_oracle_on_touched_rows():
         assert not bool((changed & ~touched).any())
         assert int(changed.sum()) > 0.99 * keys.size
     # a second run from the same tables: bitwise equal
-    tabs2 = ops.BprmfTables(U0, I0)
+    tabs2 = ops.BprmfTables(U0.clone(), I0.clone())
     loss2 = tabs2.step_sgd(plan, 0, lr)
     assert torch.equal(tabs2.U, tabs.U) and torch.equal(tabs2.I, tabs.I) and float(loss2) == float(loss)
+    del tabs, tabs2, U, I
+    torch.cuda.empty_cache()
+    # probe run (oracle/parity.py): at lr = 0.05 the step moves a row by 1e-7 of the table and the bounds above cannot fail
+    probe = ops.BprmfTables(U0, I0)
+    lp = probe.step_sgd(plan, 0, parity.probe_lr(B))
+    torch.cuda.synchronize()
+    parity.check_sgd_run("C4 10Mx10M D128 B65536, sorted plan", Uc0, Ic0, u, p, n, B, parity.probe_lr(B),
+                         parity.take_rows(probe.U, ku), parity.take_rows(probe.I, ki), lp.reshape(1), rows=(ku, ki))
+
+
+def test_c4_bprmf_d128_10m_tables_group_plan_steps_match_the_float64_reference():
+    """the same C4 shape through what ships — PipelinedSgd on group plans, four batches, so that rows are handed over from
+    step to step inside the stream — at parity.probe_lr(B) against the float64 reference on the touched rows"""
+    from whisprrec_amd import hip_ops as ops
+    dev = torch.device("cuda:0")
+    nU = nI = 10_000_000
+    D, B, nb = 128, 65536, 4
+    g = torch.Generator(device=dev).manual_seed(3407)
+    U = torch.randn(nU, D, generator=g, device=dev) * 0.05
+    I = torch.randn(nI, D, generator=g, device=dev) * 0.05
+    rng = np.random.RandomState(3408)
+    u, p, n = rng.randint(0, nU, nb * B), rng.randint(0, nI, nb * B), rng.randint(1, nI, nb * B)
+    p[:64] = p[64:128]                                                  # shared rows inside a batch ...
+    n[200:232] = p[300:332]
+    u[:16] = u[16:32]
+    u[B:B + 4096] = u[:4096]                                            # ... and rows handed over from one step to the next
+    p[2 * B:2 * B + 4096] = n[B:B + 4096]
+    p[nb * B - 64:] = nI - 1 - np.arange(64)                            # rows behind the 4 GB mark
+    ku, ki = parity.touched_rows(u, p, n)
+    Uc0, Ic0 = parity.take_rows(U, ku), parity.take_rows(I, ki)
+    T = lambda a: torch.from_numpy(a.astype(np.int32)).to(dev)
+    pipe = ops.PipelinedSgd(chunk=2, min_triplets=1)
+    handle = pipe.plan(U, [(I, T(u), T(p), T(n))], B)
+    assert handle["group"]
+    losses = torch.empty(nb, dtype=torch.float32, device=dev)
+    pipe.run(handle, 0, parity.probe_lr(B), losses)
+    torch.cuda.synchronize()
+    handle["segs"][0]["tabs"].check_chain()
+    assert pipe.stats["group_calls"] > 0 and pipe.stats["group_fallbacks"] == 0
+    parity.check_sgd_run("C4 10Mx10M D128 B65536, group plans", Uc0, Ic0, u, p, n, B, parity.probe_lr(B),
+                         parity.take_rows(U, ku), parity.take_rows(I, ki), losses, rows=(ku, ki))
 
 
 def test_c5_sasrec_item_embedding_slice_ml1m_shape():

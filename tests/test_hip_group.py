@@ -3,13 +3,16 @@ reference loop's (src/helpers/BaseRunner.py:194-200: strictly sequential, batch-
 checks are: the plan's index arrays bit-exact against their NumPy restatement (oracle.group_plan); tables and losses after
 N steps equal to the oracle's (1e-5, north_star) and to the sorted-plan stream's (rounding); tables bitwise reproducible and
 independent of how the steps are cut into calls (a stale read of a row handed over inside a launch would break exactly
-that); unusable plans say so (list overflow, id out of range)."""
+that); unusable plans say so (list overflow, id out of range).  Every oracle comparison is followed by a probe run: the same
+plan from the same tables at parity.probe_lr(B), where the update is ~1e-2 of the table, against the float64 reference with the
+error measured against the update (oracle/parity.py: at the tests' own learning rates the 1e-5 bound on the table cannot fail)."""
 import numpy as np
 import pytest
 import torch
 
 import oracle
 from conftest import rel_err
+from oracle import parity
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-5
@@ -111,6 +114,20 @@ def test_steps_match_oracle_and_are_reproducible(ops, nU, nI, D, B):
     torch.cuda.synchronize()
     assert rel_err(outs[0][0].cpu().numpy(), ref.U.cpu().numpy()) < 1e-6
     assert rel_err(outs[0][1].cpu().numpy(), ref.I.cpu().numpy()) < 1e-6
+    # probe run: one call, the update large enough to be seen
+    tabs = ops.BprmfTables(T(U, dev), T(I, dev))
+    lp = tabs.run_sgd_group(plan, 0, nb, parity.probe_lr(B))
+    torch.cuda.synchronize()
+    tabs.check_chain()
+
+    def one_step_calls(k):
+        t1 = ops.BprmfTables(T(U, dev), T(I, dev))
+        for j in range(k):
+            t1.run_sgd_group(plan, j, 1, parity.probe_lr(B))
+        torch.cuda.synchronize()
+        return t1.U, t1.I
+    parity.check_sgd_run("group %dx%d D%d B%d" % (nU, nI, D, B), U, I, u, p, n, B, parity.probe_lr(B), tabs.U, tabs.I, lp,
+                         per_step=one_step_calls)
 
 
 def test_hot_rows_take_the_slow_paths(ops):
@@ -136,6 +153,11 @@ def test_hot_rows_take_the_slow_paths(ops):
               for k in range(nb)]
     assert rel_err(losses.cpu().numpy(), np.asarray(lo_ref)) < TOL
     assert rel_err(tabs.U.cpu().numpy(), Uo) < TOL and rel_err(tabs.I.cpu().numpy(), Io) < TOL
+    tabs = ops.BprmfTables(T(U, dev), T(I, dev))                    # probe run (hot rows at the same probe_lr: oracle/parity.py)
+    lp = tabs.run_sgd_group(plan, 0, nb, parity.probe_lr(B))
+    torch.cuda.synchronize()
+    tabs.check_chain()
+    parity.check_sgd_run("group hot rows", U, I, u, p, n, B, parity.probe_lr(B), tabs.U, tabs.I, lp)
     u[B:2 * B] = 123                                                # one user for a whole batch
     assert ops.GroupPlan(T(u, dev), T(p, dev), T(n, dev), B, nU, nI).overflow
 
@@ -174,6 +196,20 @@ def test_headline_shape_rows_outside_the_batch_untouched(ops):
     l2 = again.run_sgd_group(plan, 0, nb, lr)
     torch.cuda.synchronize()
     assert torch.equal(again.U, tabs.U) and torch.equal(again.I, tabs.I) and torch.equal(l2, losses)
+    del again, mu, mi
+    probe = ops.BprmfTables(U0.clone(), I0.clone())                 # probe run: lr = 983
+    lp = probe.run_sgd_group(plan, 0, nb, parity.probe_lr(B))
+    torch.cuda.synchronize()
+    probe.check_chain()
+
+    def one_step_calls(k):
+        t1 = ops.BprmfTables(U0.clone(), I0.clone())
+        for j in range(k):
+            t1.run_sgd_group(plan, j, 1, parity.probe_lr(B))
+        torch.cuda.synchronize()
+        return t1.U, t1.I
+    parity.check_sgd_run("group headline 1Mx1M D64 B65536", U0, I0, u, p, n, B, parity.probe_lr(B), probe.U, probe.I, lp,
+                         per_step=one_step_calls)
 
 
 def test_expired_wait_is_raised_within_one_chunk(ops, g2):
@@ -238,6 +274,14 @@ def test_pipeline_falls_back_to_sorted_plans_on_skewed_ids(ops):
                   for k in range(nb)]
         assert rel_err(losses.cpu().numpy(), np.asarray(lo_ref)) < TOL
         assert rel_err(Ud.cpu().numpy(), Uo) < TOL and rel_err(Id.cpu().numpy(), Io) < TOL
+        pipe = ops.PipelinedSgd(chunk=3, min_triplets=1)              # probe run: the same stream, fall-back included
+        Ud, Id = T(U, dev), T(I, dev)
+        handle = pipe.plan(Ud, [(Id, T(u, dev), T(p, dev), T(n, dev))], B)
+        pipe.run(handle, 0, parity.probe_lr(B), losses)
+        torch.cuda.synchronize()
+        handle["segs"][0]["tabs"].check_chain()
+        assert not handle["group"] and pipe.stats["group_fallbacks"] >= 1
+        parity.check_sgd_run("pipeline, item row with %d occurrences" % hot, U, I, u, p, n, B, parity.probe_lr(B), Ud, Id, losses)
 
 
 def test_int64_epoch_columns_take_the_group_path(ops):
@@ -265,6 +309,13 @@ def test_int64_epoch_columns_take_the_group_path(ops):
               for k in range(nb)]
     assert rel_err(out[torch.int64][2].cpu().numpy(), np.asarray(lo_ref)) < TOL
     assert rel_err(out[torch.int64][0].cpu().numpy(), Uo) < TOL and rel_err(out[torch.int64][1].cpu().numpy(), Io) < TOL
+    pipe = ops.PipelinedSgd(chunk=3, min_triplets=1)                  # probe run, int64 columns
+    Ud, Id = T(U, dev), T(I, dev)
+    handle = pipe.plan(Ud, [(Id, T(u, dev).to(torch.int64), T(p, dev).to(torch.int64), T(n, dev).to(torch.int64))], B)
+    pipe.run(handle, 0, parity.probe_lr(B), losses)
+    torch.cuda.synchronize()
+    assert pipe.stats["group_calls"] > 0 and pipe.stats["group_fallbacks"] == 0
+    parity.check_sgd_run("pipeline int64 columns", U, I, u, p, n, B, parity.probe_lr(B), Ud, Id, losses)
     bad = T(p, dev).to(torch.int64)
     bad[5] = (1 << 32) + 5
     pipe = ops.PipelinedSgd(chunk=3, min_triplets=1)

@@ -11,6 +11,7 @@ import torch.distributed as dist
 
 import oracle
 from conftest import rel_err
+from oracle import parity
 
 pytestmark = pytest.mark.gpu
 
@@ -44,6 +45,10 @@ def test_sharded_world1_matches_oracle(pg):
     assert rel_err(losses, np.asarray(ref)) < 1e-5
     assert rel_err(Uf.cpu().numpy(), Uo) < 1e-5
     assert rel_err(If.cpu().numpy(), Io) < 1e-5
+    m.load_full(torch.from_numpy(U), torch.from_numpy(I))              # probe run (oracle/parity.py) from the same tables
+    losses = m.global_losses(m.run_chunk(cp, parity.probe_lr(B))).cpu().numpy()
+    Uf, If = m.gather_full()
+    parity.check_sgd_run("sharded, one rank", U, I, u, p, n, B, parity.probe_lr(B), Uf, If, losses)
 
 
 def test_shard_step_global_batch_scaling(pg):
