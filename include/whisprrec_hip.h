@@ -752,6 +752,43 @@ int32_t wr_topk_recommend(const float *user_mat, int64_t n_user_rows, const floa
                           int32_t k, int32_t *out_item, float *out_score, void *workspace, int64_t workspace_bytes,
                           void *stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * K12  InfoNCE loss and gradient of ONE side (users or items) of SGL's calc_ssl_loss (src/models/general/SGL.py:196-230,
+ *      the formula at :213-220), without the [B, n_rows] score matrix.  A = view 1, Bm = view 2, both [n_rows, D] fp32
+ *      row-major; idx int64 [B], duplicates allowed:
+ *   q_b  = A[idx_b] / max(|A[idx_b]|, 1e-12)        k_j = Bm[j] / max(|Bm[j]|, 1e-12)                     (F.normalize)
+ *   s_bj = <q_b, k_j> / tau
+ *   loss = weight * sum_b ( log sum_j exp(s_bj)  -  <q_b, k_idx_b> / tau ),   j over ALL n_rows rows
+ *   gA   = d loss / d A    non-zero only on the rows named by idx, duplicates summed
+ *   gB   = d loss / d Bm   dense: every row receives sum_b softmax_bj q_b / tau back through its normalisation, the rows
+ *                          named by idx additionally -q_b / tau
+ *   - loss [1] on the device: loss_out = (accumulate ? loss_in : 0) + this side's loss.  gA / gB [n_rows, D] are fully
+ *     written (gA is zero outside the batch rows); both NULL = loss only, and that loss has the bits of the full call's.
+ *     A, Bm, gA, gB may point into the middle of a larger contiguous table (16-byte aligned).
+ *   - Scores: the fp32 k-ordered chain of v_mfma_f32_32x32x2_f32 (f32 in, f32 accumulate), as wr_rank_eval.  The products
+ *     softmax x rows run on the same instruction.
+ *   - eps rule: a row with |x| < 1e-12 follows F.normalize's clamped branch in both directions: y = x / 1e-12 and
+ *     d loss / d x = g / 1e-12 with no projection term.
+ *   - tau domain: any finite tau > 0.  Cosines are bounded, so the kernels sum exp((c - 1) / tau), which lies in (0, 1],
+ *     and add 1 / tau back after the log; there is no running maximum and nothing overflows.  The reference's own
+ *     exp(c / tau) overflows fp32 below tau ~ 0.0113, so parity is claimed for tau >= 0.02 only; far below that a row's
+ *     whole sum can underflow.
+ *   - Determinism: no float atomics.  Item chunks and row blocks go to partials that are folded in chunk order, the loss
+ *     terms in a fixed order, and the rows of a duplicated id are summed in ascending batch position by one writer
+ *     (a scan of idx per duplicated row: cheap while duplicates are few, quadratic in B when B >> n_rows).  Same inputs,
+ *     same bits — loss, gA and gB.
+ *   - Bad ids: an id outside [0, n_rows) is clamped to the nearest row, never dereferenced, and err_word[0] |= 1
+ *     (err_word may be NULL; the caller clears it).
+ *   - D in {32, 64, 128} (wr_infonce_supported); any other value is refused before a launch, like every argument error.
+ *   - workspace >= wr_infonce_workspace_bytes(n_rows, B, D), 16-byte aligned.  The bound grows with n_rows * D, with B * D
+ *     and with a fixed number of [row, D] chunk partials — never with B * n_rows — and never decreases as n_rows or B grow.
+ *   - No host round trip, no allocation: capturable into a hipGraph. */
+int32_t wr_infonce_supported(int32_t D);
+int64_t wr_infonce_workspace_bytes(int64_t n_rows, int64_t B, int32_t D);
+int32_t wr_infonce_loss_grad(const float *A, const float *Bm, int64_t n_rows, int32_t D, const int64_t *idx, int64_t B,
+                             float tau, float weight, float *loss, int32_t accumulate, float *gA, float *gB,
+                             int32_t *err_word, void *workspace, int64_t workspace_bytes, void *stream);
+
 /* LightGCN.predict's per-batch tail in two launches (src/models/general/LightGCN.py:156-175, src/utils/loss.py:37-39,94-98):
  *   loss[0] = mean_b( -log(1e-10 + sigmoid(<Ua[u_b], Ia[p_b]> - <Ua[u_b], Ia[n_b]>)) )
  *             + reg_weight * (||U0[u]||_F + ||I0[p]||_F + ||I0[n]||_F) / B

@@ -174,6 +174,10 @@ SIGNATURES = {
     "wr_topk_workspace_bytes": (c_i64, [c_i64, c_i64, c_i32, c_i32]),
     "wr_topk_recommend": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i32, c_vp, c_i64, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_i64,
                                   c_vp]),
+    "wr_infonce_supported": (c_i32, [c_i32]),
+    "wr_infonce_workspace_bytes": (c_i64, [c_i64, c_i64, c_i32]),
+    "wr_infonce_loss_grad": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_vp, c_i64, c_f32, c_f32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp,
+                                     c_i64, c_vp]),
     "wr_lightgcn_loss_workspace_bytes": (c_i64, [c_i64]),
     "wr_lightgcn_loss": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_vp, c_vp, c_vp, c_i64, c_f32, c_vp, c_vp, c_vp,
                                  c_i64, c_vp]),

@@ -1176,6 +1176,79 @@ def topk_recommend(user_mat, item_tab, users, k, mask_ptr=None, mask_idx=None):
     return items.to(torch.int64), scores
 
 
+# ----------------------------------------------------------------------------------------------- InfoNCE (SGL)
+_INFONCE_WS = {}        # (device, stream, n, B, D) -> (workspace bytes, error word): nothing is allocated after the first call
+
+
+def infonce_supports(D):
+    """embedding sizes wr_infonce_loss_grad takes (wr_infonce_supported)"""
+    return bool(abi.lib().wr_infonce_supported(int(D)))
+
+
+def infonce_workspace_bytes(n, B, D):
+    return abi.check_size(abi.lib().wr_infonce_workspace_bytes(int(n), int(B), int(D)), "wr_infonce_workspace_bytes")
+
+
+def infonce_loss_grad(A, Bm, idx, tau, weight=1.0, *, loss=None, grads=True, validate=True, out=None):
+    """One side of SGL's calc_ssl_loss without the [B, n] score matrix (wr_infonce_loss_grad):
+    loss = weight * sum_b (log sum_j exp(<q_b, k_j> / tau) - <q_b, k_idx_b> / tau) over the L2-normalised rows q of A[idx]
+    and k of Bm, and its gradients w.r.t. A and Bm.  `loss`: a (1,) device tensor to ADD this side's loss to (None = a
+    fresh one).  `grads=False`: loss only.  `out=(gA, gB)`: [n, D] tensors (slices of a larger table are fine) to write
+    instead of fresh ones.  `validate=False` skips the read-back of the error word (ids already range-checked).
+    Returns (loss, gA, gB)."""
+    _req(A, torch.float32, "A", 2)
+    _req(Bm, torch.float32, "Bm", 2)
+    ids = _idx64(idx.reshape(-1), "idx")
+    if tuple(A.shape) != tuple(Bm.shape):
+        raise ValueError("A and Bm must have the same shape (got %s, %s)" % (tuple(A.shape), tuple(Bm.shape)))
+    n, D = int(A.shape[0]), int(A.shape[1])
+    B = ids.numel()
+    if not infonce_supports(D):
+        raise abi.WhisprRecHipError("infonce_loss_grad does not support D=%d (D in {32, 64, 128})" % D)
+    if not (float(tau) > 0.0):
+        raise ValueError("tau must be positive (got %r)" % (tau,))
+    dev = A.device
+    accumulate = loss is not None
+    if accumulate:
+        _req(loss, torch.float32, "loss")
+        if loss.numel() != 1:
+            raise ValueError("loss must hold one element")
+    else:
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+    gA = gB = None
+    if grads:
+        if out is not None:
+            gA, gB = out
+            for t, nm in ((gA, "gA"), (gB, "gB")):
+                _req(t, torch.float32, nm, 2)
+                if tuple(t.shape) != (n, D):
+                    raise ValueError("%s must be [%d, %d]" % (nm, n, D))
+        else:
+            gA = torch.empty((n, D), dtype=torch.float32, device=dev)
+            gB = torch.empty((n, D), dtype=torch.float32, device=dev)
+    L = abi.lib()
+    key = (str(dev), torch.cuda.current_stream(dev).cuda_stream, n, B, D)
+    slot = _INFONCE_WS.get(key)
+    if slot is None:
+        nbytes = infonce_workspace_bytes(n, B, D)
+        slot = (torch.empty(nbytes, dtype=torch.uint8, device=dev), torch.zeros(1, dtype=torch.int32, device=dev))
+        _INFONCE_WS[key] = slot
+    ws, err = slot
+    if validate:
+        err.zero_()
+    abi.check(L.wr_infonce_loss_grad(_p(A), _p(Bm), n, D, _p(ids), B, float(tau), float(weight), _p(loss), int(accumulate),
+                                     _p(gA), _p(gB), _p(err) if validate else None, _p(ws), ws.numel(), _stream()),
+              "wr_infonce_loss_grad")
+    if validate and int(err.item()) != 0:
+        raise IndexError("infonce_loss_grad: idx holds an id outside [0, %d)" % n)
+    return loss, gA, gB
+
+
+def infonce_release_workspaces():
+    """drop the cached workspaces (they are as large as a table at big n)"""
+    _INFONCE_WS.clear()
+
+
 # ----------------------------------------------------------------------------------------------- optimizers
 def sgd_dense(tab, grad, lr, l2=0.0, stamp=None, step_id=0):
     abi.check(abi.lib().wr_sgd_dense(_p(_req(tab, torch.float32, "tab", 2)), tab.shape[0], tab.shape[1],

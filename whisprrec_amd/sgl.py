@@ -14,10 +14,16 @@ What changes underneath:
   * views are NOT symmetric (the reference drops (u,i) and (i,u) independently, and normalises by row sums on both
     sides, SGL.py:117-124) — so each view keeps a CSR of its transpose for the backward propagation;
   * the three propagations (:232-239) and their backward run on the chunked CSR SpMM kernel (``wr_spmm_csr_chunked``), row
-    gathers / the deterministic sorted scatter-add / EmbLoss on the HIP row kernels; the InfoNCE term (:196-230) is two
-    plain [B, n] GEMMs with exp/sum around them and stays on rocBLAS through ``torch.matmul``.
+    gathers / the deterministic sorted scatter-add / EmbLoss on the HIP row kernels;
+  * the InfoNCE term (:196-230) has two paths.  ``--ssl_native 0`` (default): the reference's formula as written — two
+    [B, n] GEMMs on rocBLAS through ``torch.matmul`` with exp / sum / log around them and ``torch.autograd.grad`` over
+    the two propagated tables, which keeps several [B, n] matrices alive.  ``--ssl_native 1``: one call per side of
+    ``hip_ops.infonce_loss_grad`` (wr_infonce.hip) — loss and both gradients on the matrix cores without any [B, n]
+    array, bitwise reproducible, written straight into the gradient tables of the two views; an embedding size the
+    kernel does not take (it takes 32, 64, 128) is logged once and keeps the stock path.
 No CPU path.
 """
+import logging
 import random
 
 import numpy as np
@@ -159,6 +165,8 @@ def make_sgl(general_model_cls):
             parser.add_argument("--ssl_tau", type=float, default=0.1, help="The temperature in softmax.")
             parser.add_argument("--ssl_weight", type=float, default=0.05, help="The hyperparameter to control the strengths of SSL.")
             parser.add_argument("--drop_ratio", type=float, default=0.1, help="The dropout ratio.")
+            parser.add_argument("--ssl_native", type=int, default=0, choices=[0, 1],
+                                help="1: InfoNCE loss and gradient by the fused HIP kernels (no [B, n] matrix); 0: torch GEMMs + autograd.")
             return general_model_cls.parse_model_args(parser)
 
         def __init__(self, args, corpus):
@@ -171,6 +179,8 @@ def make_sgl(general_model_cls):
             self.reg_weight = float(args.reg_weight)
             self.type = str(args.type)
             self.ssl_weight, self.ssl_tau, self.drop_ratio = args.ssl_weight, args.ssl_tau, args.drop_ratio
+            self.ssl_native = bool(int(getattr(args, "ssl_native", 0)))
+            self._ssl_native_ok = None   # decided at the first step: the library says which embedding sizes it takes
             self.user_embedding = nn.Embedding(self.n_users, self.emb_size)
             self.item_embedding = nn.Embedding(self.n_items, self.emb_size)
             # plain attributes like the reference's graphs (absent from state_dict)
@@ -241,6 +251,28 @@ def make_sgl(general_model_cls):
 
             return (side(p, E1[nU:], E2[nU:]) + side(u, E1[:nU], E2[:nU])) * self.ssl_weight
 
+        def _use_ssl_native(self):
+            if not self.ssl_native:
+                return False
+            if self._ssl_native_ok is None:
+                self._ssl_native_ok = hip_ops.infonce_supports(self.emb_size)
+                if not self._ssl_native_ok:
+                    logging.warning("--ssl_native 1: the InfoNCE kernels do not take embedding_size=%d; keeping the torch path",
+                                    self.emb_size)
+            return self._ssl_native_ok
+
+        def _ssl_native_grad(self, u, p, E1, E2):
+            """calc_ssl_loss and its gradient w.r.t. both views by wr_infonce_loss_grad: items first, then users, as the
+            reference adds them; each side writes its own row range of the two gradient tables"""
+            nU = self.n_users
+            gE1, gE2 = torch.empty_like(E1), torch.empty_like(E2)
+            check = not getattr(self, "_trusted_indices", False)
+            ssl, _, _ = hip_ops.infonce_loss_grad(E1[nU:], E2[nU:], p, self.ssl_tau, self.ssl_weight, out=(gE1[nU:], gE2[nU:]),
+                                                  validate=check)
+            hip_ops.infonce_loss_grad(E1[:nU], E2[:nU], u, self.ssl_tau, self.ssl_weight, loss=ssl, out=(gE1[:nU], gE2[:nU]),
+                                      validate=check)
+            return ssl[0], gE1, gE2
+
         @torch.no_grad()
         def _loss_and_grad(self, u, p, n):
             nU, L, B = self.n_users, self.gcn_layers, u.numel()
@@ -260,12 +292,16 @@ def make_sgl(general_model_cls):
             # --- EmbLoss on the raw rows (utils/loss.py:94-98)
             sq = hip_ops.embloss_sumsq(U0, I0, u, p, n)
             reg = torch.sqrt(sq).sum() / B
-            # --- InfoNCE between the two views: plain GEMMs, autograd over the two propagated tables only
-            with torch.enable_grad():
-                E1r, E2r = E1.detach().requires_grad_(True), E2.detach().requires_grad_(True)
-                ssl = self._ssl(u, p, E1r, E2r)
-                gE1, gE2 = torch.autograd.grad(ssl, [E1r, E2r])
-            loss = l1 + reg * self.reg_weight + ssl.detach()
+            # --- InfoNCE between the two views
+            if self._use_ssl_native():
+                ssl, gE1, gE2 = self._ssl_native_grad(u, p, E1, E2)
+            else:   # plain GEMMs, autograd over the two propagated tables only
+                with torch.enable_grad():
+                    E1r, E2r = E1.detach().requires_grad_(True), E2.detach().requires_grad_(True)
+                    ssl = self._ssl(u, p, E1r, E2r)
+                    gE1, gE2 = torch.autograd.grad(ssl, [E1r, E2r])
+                ssl = ssl.detach()
+            loss = l1 + reg * self.reg_weight + ssl
             # --- back through the three propagations (views are not symmetric: transposed CSR)
             gE0 = gm.propagate(gEm, L, transpose=True)
             gE0 += g1.propagate(gE1.contiguous(), L, transpose=True)
