@@ -4,7 +4,7 @@
 // L2-normalised (F.normalize, eps 1e-12), every batch row is scored against every row of view 2, and
 //     loss = weight * sum_b ( log sum_j exp(<q_b, k_j> / tau)  -  <q_b, k_idx_b> / tau ).
 // The reference forms e1.matmul(all2.T) and lets autograd keep it and its exp alive.  Here the scores exist only as 32x32
-// accumulator tiles of v_mfma_f32_32x32x2_f32 (f32 in, f32 accumulate: the k-ordered fma chain wr_eval.hip uses):
+// accumulator tiles of v_mfma_f32_32x32x2_f32 (f32 in, f32 accumulate: the k-ordered fma chain of wr_score_tiles.h):
 //
 //   prep        k_j = Bm[j] / max(|Bm[j]|, eps) for every row (workspace, [n, D]) and q_b likewise for the batch rows; ids
 //               outside [0, n) are clamped and reported; owner[id] = first batch position that names the row
@@ -22,13 +22,11 @@
 //   scatter     rows named by the batch: gA[id] = sum of the per-position gradients, gB[id] += sum of the positive terms, by
 //               the owner position, in ascending position order
 // No float atomics anywhere: every sum has a fixed order, the results are bitwise reproducible.  No host round trip.
-#include "wr_common.h"
+#include "wr_score_tiles.h"
 
 namespace wr {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int kNceRows = 128;             // resident rows per workgroup (32 per wave)
+constexpr int kNceRows = kScoreRows;      // resident rows per workgroup (32 per wave)
 constexpr int64_t kNceTargetWg = 1024;    // workgroups a pass aims at when it splits the streamed side into chunks
 constexpr float kNceEps = 1e-12f;         // F.normalize's eps
 constexpr int kNceTeam = 16;              // lanes per row in the row kernels
@@ -163,8 +161,7 @@ __global__ __launch_bounds__(kBlock, 2) void nce_pass_kernel(const float *__rest
                                                             int64_t nt, const float *__restrict__ tscale, float escale,
                                                             int64_t chunk_rows, float *__restrict__ part,
                                                             float *__restrict__ zpart) {
-    constexpr int D = 2 * KS, LDW = D + 1, D4 = D / 4, C = TS / 32, NB = D / 32;
-    constexpr int NLOAD = (TS * D4 + kBlock - 1) / kBlock;               // float4 loads per thread and tile
+    constexpr int D = 2 * KS, LDW = D + 1, C = TS / 32, NB = D / 32;
     __shared__ float it[2][TS * LDW];
     __shared__ float sc[2][TS];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -184,31 +181,17 @@ __global__ __launch_bounds__(kBlock, 2) void nce_pass_kernel(const float *__rest
 #pragma unroll
     for (int b = 0; b < NB; ++b) out[b] = f32x16{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     float z = 0.f;
-    float4 stage[NLOAD];
+    TileStager<D, TS> stager;
     float sstage = 0.f;
     auto fetch = [&](int64_t j0) {
-#pragma unroll
-        for (int i = 0; i < NLOAD; ++i) {
-            const int f = threadIdx.x + i * kBlock;
-            const int r = f / D4, k4 = f - r * D4;
-            stage[i] = (f < TS * D4 && j0 + r < c1)
-                           ? reinterpret_cast<const float4 *>(T + (j0 + r) * (int64_t)D)[k4] : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
+        stager.fetch(T, j0, c1);
         if (threadIdx.x < TS) {
             const int64_t r = j0 + threadIdx.x;
             sstage = (r < c1) ? (tscale != nullptr ? tscale[r] : 1.0f) : 0.f;
         }
     };
     auto deposit = [&](int buf) {
-#pragma unroll
-        for (int i = 0; i < NLOAD; ++i) {
-            const int f = threadIdx.x + i * kBlock;
-            if (f < TS * D4) {
-                const int r = f / D4, k4 = f - r * D4;
-                float *dst = &it[buf][r * LDW + 4 * k4];
-                dst[0] = stage[i].x; dst[1] = stage[i].y; dst[2] = stage[i].z; dst[3] = stage[i].w;
-            }
-        }
+        stager.deposit(it[buf]);
         if (threadIdx.x < TS) sc[buf][threadIdx.x] = sstage;
     };
     fetch(c0);
@@ -218,23 +201,14 @@ __global__ __launch_bounds__(kBlock, 2) void nce_pass_kernel(const float *__rest
     for (int64_t j0 = c0; j0 < c1; j0 += TS, buf ^= 1) {
         const bool more = j0 + TS < c1;
         if (more) fetch(j0 + TS);                                       // global loads fly while the matrix cores work
-        const float *trow = &it[buf][col * LDW + half];                 // A[i = lane&31][k = 2s + (lane>>5)] of block 0
+        // acc[c][reg] = score(streamed row c*32 + acc_row(reg, half), resident row lane&31)
         f32x16 acc[C];
-#pragma unroll
-        for (int c = 0; c < C; ++c) acc[c] = f32x16{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-        for (int s = 0; s < KS; ++s) {
-#pragma unroll
-            for (int c = 0; c < C; ++c)
-                acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(trow[c * 32 * LDW + 2 * s], a[s], acc[c], 0, 0, 0);
-        }
-        // acc[c][reg] = score(streamed row c*32 + (reg&3) + 8*(reg>>2) + 4*half, resident row lane&31)
+        score_tiles<KS, C, LDW, true>(a, &it[buf][col * LDW + half], acc);   // A[i = lane&31][k = 2s + (lane>>5)] of block 0
 #pragma unroll
         for (int c = 0; c < C; ++c) {
 #pragma unroll
             for (int reg = 0; reg < 16; ++reg) {
-                const int r = c * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * half;
-                const float w = __builtin_amdgcn_exp2f((acc[c][reg] - 1.0f) * escale) * sc[buf][r];
+                const float w = __builtin_amdgcn_exp2f((acc[c][reg] - 1.0f) * escale) * sc[buf][c * 32 + acc_row(reg, half)];
                 z += w;
                 acc[c][reg] = w;
             }
@@ -246,8 +220,8 @@ __global__ __launch_bounds__(kBlock, 2) void nce_pass_kernel(const float *__rest
             for (int c = 0; c < C; ++c) {
 #pragma unroll
                 for (int reg = 0; reg < 16; ++reg) {
-                    const int r = c * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * half;
-                    const float *brow = &it[buf][r * LDW + col];         // B[k = half][j = d = lane&31 (+ 32 b)]
+                    // B[k = half][j = d = lane&31 (+ 32 b)]
+                    const float *brow = &it[buf][(c * 32 + acc_row(reg, half)) * LDW + col];
 #pragma unroll
                     for (int b = 0; b < NB; ++b)
                         out[b] = __builtin_amdgcn_mfma_f32_32x32x2f32(acc[c][reg], brow[b * 32], out[b], 0, 0, 0);
@@ -267,7 +241,7 @@ __global__ __launch_bounds__(kBlock, 2) void nce_pass_kernel(const float *__rest
         for (int b = 0; b < NB; ++b) {
 #pragma unroll
             for (int reg = 0; reg < 16; ++reg) {
-                const int64_t e = e0 + wave * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * half;
+                const int64_t e = e0 + wave * 32 + acc_row(reg, half);
                 if (e < nr) part[((int64_t)blockIdx.y * nr + e) * D + b * 32 + col] = out[b][reg];
             }
         }
@@ -429,15 +403,11 @@ static inline bool nce_shape_ok(int64_t n, int64_t B) {
 template <bool GRAD>
 static void nce_launch_pass(int32_t D, dim3 grid, hipStream_t stream, const float *R, int64_t nr, const float *T, int64_t nt,
                             const float *tscale, float escale, int64_t chunk_rows, float *part, float *zpart) {
-    if (D == 32)
-        hipLaunchKernelGGL((nce_pass_kernel<16, 64, GRAD>), grid, dim3(kBlock), 0, stream, R, nr, T, nt, tscale, escale, chunk_rows,
-                           part, zpart);
-    else if (D == 64)
-        hipLaunchKernelGGL((nce_pass_kernel<32, 64, GRAD>), grid, dim3(kBlock), 0, stream, R, nr, T, nt, tscale, escale, chunk_rows,
-                           part, zpart);
-    else
-        hipLaunchKernelGGL((nce_pass_kernel<64, 32, GRAD>), grid, dim3(kBlock), 0, stream, R, nr, T, nt, tscale, escale, chunk_rows,
-                           part, zpart);
+#define WR_NCE_PASS(KS_)                                                                                              \
+    hipLaunchKernelGGL((nce_pass_kernel<KS_, ((KS_) <= 32 ? 64 : 32), GRAD>), grid, dim3(kBlock), 0, stream, R, nr, T, nt, tscale, \
+                       escale, chunk_rows, part, zpart)
+    WR_DISPATCH_KS(D, 16, 64, WR_NCE_PASS);                             // the tile height is nce_tile(D)
+#undef WR_NCE_PASS
 }
 
 }  // namespace wr

@@ -2,8 +2,8 @@
 //
 // The reference's (commented-out) save_rec_results (src/main.py:83-102) sorts each row of full_predict with the user's
 // clicked items at -inf and keeps the first K.  Here the scores come from the same v_mfma_f32_32x32x2_f32 tiles as
-// wr_rank_eval (wr_eval.hip): an exact k-ordered fp32 chain, so a returned score is bitwise equal to wr_rank_eval's
-// target_score for that pair.  Each score is packed into one 64-bit key
+// wr_rank_eval (the scan of wr_score_tiles.h): an exact k-ordered fp32 chain, so a returned score is bitwise equal to
+// wr_rank_eval's target_score for that pair.  Each score is packed into one 64-bit key
 //     key = (orderable(score) << 32) | (0xFFFFFFFF - item),
 // so a single unsigned compare orders by score descending, then item ascending; key 0 is the padding (-1, -inf).
 //
@@ -14,16 +14,12 @@
 // keeps the K best as the row's list and raises the threshold.  Items are visited in ascending order inside a chunk, so an
 // item whose score only ties the threshold has the larger id and loses: the fast test is a strict compare of the score part.
 // Phase 2 (topk_merge_kernel): one wave per row folds the chunk lists together with the same sort and decodes.
-#include "wr_common.h"
+#include "wr_score_tiles.h"
 
 namespace wr {
 
-typedef float tk_f32x16 __attribute__((ext_vector_type(16)));
 typedef unsigned long long u64;
 
-constexpr int kTopkRows = 128;              // query rows per workgroup (32 per wave)
-constexpr int kTopkTile = 64;               // items per tile, register-operand kernel (double-buffered)
-constexpr int kTopkTileG = 32;              // items per tile, LDS-operand kernel
 constexpr int kTopkSlots = 256 * 2;         // 256 CUs x 2 resident workgroups of the register-operand kernel (<= 256 VGPRs)
 constexpr int64_t kTopkMinChunk = 4096;     // items per chunk at least (fewer, longer chunks: fewer candidates and lists)
 constexpr int64_t kTopkMaxChunks = 64;
@@ -121,13 +117,32 @@ struct TopkRows {
     int k, trigger, lane;
 };
 
+// The scan kernels' prologue: the wave's view of the workgroup's thresholds and counts (thr_s, cnt_s: [kScoreRows] LDS, set
+// here, visible after the scan's first barrier) and of its regions of M keys in the workspace, lists emptied.  A merge is
+// due when a row's staging could overflow on the next tile of `tile` items.
 template <int E>
-__device__ __forceinline__ void topk_init_rows(const TopkRows &w, int64_t e_first, int64_t n) {
+__device__ __forceinline__ TopkRows topk_rows(u64 *ws, int nc, int k, int tile, int64_t n, unsigned *thr_s, int *cnt_s) {
+    constexpr int M = 64 * E;
+    const int wave = threadIdx.x >> 6;
+    const int64_t e0 = (int64_t)blockIdx.x * kScoreRows;
+    TopkRows w;
+    w.stride = (int64_t)nc * M;
+    w.base = ws + ((e0 + wave * 32) * nc + blockIdx.y) * (int64_t)M;
+    w.thr = thr_s + wave * 32;
+    w.cnt = cnt_s + wave * 32;
+    w.k = k;
+    w.trigger = M - k - tile;
+    w.lane = threadIdx.x & 63;
+    if (threadIdx.x < kScoreRows) {
+        thr_s[threadIdx.x] = (e0 + threadIdx.x < n) ? 0u : 0xFFFFFFFFu;
+        cnt_s[threadIdx.x] = 0;
+    }
     for (int r = 0; r < 32; ++r) {
-        if (e_first + r >= n) break;
+        if (e0 + wave * 32 + r >= n) break;
         u64 *b = w.base + r * w.stride;
         for (int j = w.lane; j < w.k; j += 64) b[j] = 0ull;
     }
+    return w;
 }
 
 // merge every row whose staging holds more than `above` keys
@@ -146,10 +161,10 @@ __device__ __forceinline__ void topk_merge_rows(const TopkRows &w, int above) {
     }
 }
 
-// One tile's C column blocks of 32 x 32 scores (this lane: rows (reg&3) + 8*(reg>>2) + 4*half, column j0 + 32c + col).
-// masked(c, row) and the table end only matter when `plain` is false.
-template <int C, int E, typename Masked>
-__device__ __forceinline__ void topk_absorb(const TopkRows &w, const tk_f32x16 (&acc)[C], int64_t j0, bool plain,
+// The score scan's consumer.  One tile's C column blocks of 32 x 32 scores (this lane: rows acc_row(reg, half), column
+// j0 + 32c + col).  masked(c, row) and the table end only matter when `plain` is false.
+template <int E, int C, typename Masked>
+__device__ __forceinline__ void topk_absorb(const TopkRows &w, const f32x16 (&acc)[C], int64_t j0, bool plain,
                                             int64_t n_items, Masked masked) {
     const int col = w.lane & 31, half = w.lane >> 5;
     uint32_t th[16];
@@ -161,7 +176,7 @@ __device__ __forceinline__ void topk_absorb(const TopkRows &w, const tk_f32x16 (
     auto cand = [&](int c, int reg) -> bool {
         bool ok = ord_of(acc[c][reg]) > th[reg];
         if (!plain) {
-            const int row = (reg & 3) + 8 * (reg >> 2) + 4 * half;
+            const int row = acc_row(reg, half);
             ok = ok && j0 + c * 32 + col < n_items && !masked(c, row);
         }
         return ok;
@@ -176,7 +191,7 @@ __device__ __forceinline__ void topk_absorb(const TopkRows &w, const tk_f32x16 (
     bool full = false;
 #pragma unroll
     for (int reg = 0; reg < 16; ++reg) {
-        const int row = (reg & 3) + 8 * (reg >> 2) + 4 * half;
+        const int row = acc_row(reg, half);
         int cnt = w.cnt[row];
         u64 *dst = w.base + row * w.stride + w.k;
 #pragma unroll
@@ -198,8 +213,7 @@ __device__ __forceinline__ void topk_absorb(const TopkRows &w, const tk_f32x16 (
     }
 }
 
-// Register-operand kernel, D = 2*KS in {8, 16, 32, 64}: the structure of eval_rank_kernel_rega (A in registers, item tiles
-// of 64 double-buffered in LDS, per-row mask bitmaps with a per-slab `anymask` skip).
+// Register-operand kernel, D = 2*KS in {8, 16, 32, 64}.
 // 2 workgroups per CU: at 3 (<= 168 VGPRs) the staging and merge path spills to scratch.
 template <int KS, int E>
 __global__ __launch_bounds__(kBlock, 2) void topk_scan_kernel_rega(const float *__restrict__ U, const float *__restrict__ I,
@@ -207,197 +221,31 @@ __global__ __launch_bounds__(kBlock, 2) void topk_scan_kernel_rega(const float *
                                                                  const int64_t *__restrict__ mask_ptr,
                                                                  const int *__restrict__ mask_idx, int k, int64_t chunk,
                                                                  int nc, u64 *ws) {
-    constexpr int D = 2 * KS, LDW = D + 1, D4 = D / 4, M = 64 * E;
-    constexpr int NLOAD = (kTopkTile * D4 + kBlock - 1) / kBlock;
-    __shared__ float it[2][kTopkTile * LDW];
-    __shared__ unsigned rowmask[2][kTopkTile / 32][kTopkRows];
-    __shared__ unsigned anymask[2][kBlock / 64];
-    __shared__ __attribute__((aligned(16))) unsigned thr_s[kTopkRows];
-    __shared__ int cnt_s[kTopkRows];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int col = lane & 31, half = lane >> 5;
-    const int64_t e0 = (int64_t)blockIdx.x * kTopkRows;
-    const int64_t c0 = (int64_t)blockIdx.y * chunk;
-    const int64_t c1 = (c0 + chunk < n_items) ? c0 + chunk : n_items;
-    TopkRows w;
-    w.stride = (int64_t)nc * M;
-    w.base = ws + ((e0 + wave * 32) * nc + blockIdx.y) * (int64_t)M;
-    w.thr = thr_s + wave * 32;
-    w.cnt = cnt_s + wave * 32;
-    w.k = k;
-    w.trigger = M - k - kTopkTile;
-    w.lane = lane;
-    if (threadIdx.x < kTopkRows) {
-        thr_s[threadIdx.x] = (e0 + threadIdx.x < n) ? 0u : 0xFFFFFFFFu;
-        cnt_s[threadIdx.x] = 0;
-    }
-    topk_init_rows<E>(w, e0 + wave * 32, n);
-    float a[KS];
-    {
-        const int64_t e = e0 + wave * 32 + col;
-        const float *urow = U + ((e < n) ? qu[e] : 0) * (int64_t)D + half;
-#pragma unroll
-        for (int s = 0; s < KS; ++s) a[s] = (e < n) ? urow[2 * s] : 0.f;
-    }
-    int64_t cur = 0, cend = 0;
-    if (threadIdx.x < kTopkRows && mask_ptr != nullptr && e0 + threadIdx.x < n) {
-        const int64_t uu = qu[e0 + threadIdx.x];
-        int64_t lo = mask_ptr[uu], hi = mask_ptr[uu + 1];
-        cend = hi;
-        while (lo < hi) {
-            const int64_t mid = (lo + hi) >> 1;
-            if ((int64_t)mask_idx[mid] < c0) lo = mid + 1; else hi = mid;
-        }
-        cur = lo;
-    }
-    int nxt = (cur < cend) ? mask_idx[cur] : 0x7fffffff;
-    float4 stage[NLOAD];
-    auto fetch = [&](int64_t j0) {
-#pragma unroll
-        for (int i = 0; i < NLOAD; ++i) {
-            const int f = threadIdx.x + i * kBlock;
-            const int r = f / D4, k4 = f - r * D4;
-            stage[i] = (f < kTopkTile * D4 && j0 + r < n_items)
-                           ? reinterpret_cast<const float4 *>(I + (j0 + r) * (int64_t)D)[k4] : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    };
-    auto deposit = [&](int buf, int64_t j0) {
-#pragma unroll
-        for (int i = 0; i < NLOAD; ++i) {
-            const int f = threadIdx.x + i * kBlock;
-            if (f < kTopkTile * D4) {
-                const int r = f / D4, k4 = f - r * D4;
-                float *dst = &it[buf][r * LDW + 4 * k4];
-                dst[0] = stage[i].x; dst[1] = stage[i].y; dst[2] = stage[i].z; dst[3] = stage[i].w;
-            }
-        }
-        if (threadIdx.x < kTopkRows) {
-            unsigned m[kTopkTile / 32];
-#pragma unroll
-            for (int c = 0; c < kTopkTile / 32; ++c) m[c] = 0;
-            while ((int64_t)nxt < j0 + kTopkTile) {
-                const int64_t d = (int64_t)nxt - j0;
-                if (d >= 0) m[d >> 5] |= 1u << (unsigned)(d & 31);
-                ++cur;
-                nxt = (cur < cend) ? mask_idx[cur] : 0x7fffffff;
-            }
-            unsigned any = 0;
-#pragma unroll
-            for (int c = 0; c < kTopkTile / 32; ++c) {
-                rowmask[buf][c][threadIdx.x] = m[c];
-                any |= m[c];
-            }
-            const unsigned long long bal = __ballot(any != 0);
-            if (lane == 0) {
-                anymask[buf][2 * wave] = (unsigned)(bal & 0xffffffffull) != 0;
-                anymask[buf][2 * wave + 1] = (unsigned)(bal >> 32) != 0;
-            }
-        }
-    };
-    fetch(c0);
-    deposit(0, c0);
-    __syncthreads();
-    int buf = 0;
-    for (int64_t j0 = c0; j0 < c1; j0 += kTopkTile, buf ^= 1) {
-        const bool more = j0 + kTopkTile < c1;
-        if (more) fetch(j0 + kTopkTile);
-        {
-            constexpr int C = kTopkTile / 32;
-            const float *bcol = &it[buf][col * LDW + half];
-            tk_f32x16 acc[C];
-#pragma unroll
-            for (int c = 0; c < C; ++c) acc[c] = tk_f32x16{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-            for (int s = 0; s < KS; ++s) {
-#pragma unroll
-                for (int c = 0; c < C; ++c)
-                    acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s], bcol[c * 32 * LDW + 2 * s], acc[c], 0, 0, 0);
-            }
-            const bool plain = anymask[buf][wave] == 0 && j0 + kTopkTile <= n_items;
-            const int b = buf;
-            topk_absorb<C, E>(w, acc, j0, plain, n_items,
-                              [&](int c, int row) { return ((rowmask[b][c][wave * 32 + row] >> col) & 1u) != 0; });
-        }
-        if (more) deposit(buf ^ 1, j0 + kTopkTile);
-        __syncthreads();
-    }
+    __shared__ __attribute__((aligned(16))) unsigned thr_s[kScoreRows];
+    __shared__ int cnt_s[kScoreRows];
+    const TopkRows w = topk_rows<E>(ws, nc, k, kScoreTile, n, thr_s, cnt_s);
+    score_scan_rega<KS>(U, I, n_items, qu, n, mask_ptr, mask_idx, (int64_t)blockIdx.y * chunk, chunk,
+                        [&](const auto &acc, int64_t j0, bool plain, auto masked) {
+                            topk_absorb<E>(w, acc, j0, plain, n_items, masked);
+                        });
     wave_sync();
     topk_merge_rows<E>(w, 0);
 }
 
-// LDS-operand kernel for any other D (multiple of 4, <= 252): the structure of eval_rank_kernel (query rows and one
-// 32-item tile staged in LDS with padded rows).
+// LDS-operand kernel for any other D (multiple of 4, <= 252); thresholds and counts are the scan's side words.
 template <int E>
 __global__ __launch_bounds__(kBlock) void topk_scan_kernel(const float *__restrict__ U, const float *__restrict__ I, int D,
                                                            int64_t n_items, const int64_t *__restrict__ qu, int64_t n,
                                                            const int64_t *__restrict__ mask_ptr,
                                                            const int *__restrict__ mask_idx, int k, int64_t chunk, int nc,
                                                            u64 *ws) {
-    constexpr int M = 64 * E;
-    extern __shared__ float lds[];
-    const int ldw = D + 1;
-    float *ue = lds;                                                    // [kTopkRows][ldw]
-    float *it = lds + kTopkRows * ldw;                                  // [32][ldw]
-    unsigned *rowmask = reinterpret_cast<unsigned *>(it + kTopkTileG * ldw);   // [kTopkRows]
-    unsigned *thr_s = rowmask + kTopkRows;                              // [kTopkRows], 16-byte aligned: (160 ldw + 128) * 4
-    int *cnt_s = reinterpret_cast<int *>(thr_s + kTopkRows);            // [kTopkRows]
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int col = lane & 31, half = lane >> 5;
-    const int64_t e0 = (int64_t)blockIdx.x * kTopkRows;
-    const int64_t c0 = (int64_t)blockIdx.y * chunk;
-    const int64_t c1 = (c0 + chunk < n_items) ? c0 + chunk : n_items;
-    TopkRows w;
-    w.stride = (int64_t)nc * M;
-    w.base = ws + ((e0 + wave * 32) * nc + blockIdx.y) * (int64_t)M;
-    w.thr = thr_s + wave * 32;
-    w.cnt = cnt_s + wave * 32;
-    w.k = k;
-    w.trigger = M - k - kTopkTileG;
-    w.lane = lane;
-    if (threadIdx.x < kTopkRows) {
-        thr_s[threadIdx.x] = (e0 + threadIdx.x < n) ? 0u : 0xFFFFFFFFu;
-        cnt_s[threadIdx.x] = 0;
-    }
-    topk_init_rows<E>(w, e0 + wave * 32, n);
-    for (int idx = threadIdx.x; idx < kTopkRows * D; idx += kBlock) {
-        const int r = idx / D, kk = idx - r * D;
-        const int64_t e = e0 + r;
-        ue[r * ldw + kk] = (e < n) ? U[qu[e] * (int64_t)D + kk] : 0.f;
-    }
-    int64_t cur = 0, cend = 0;
-    if (threadIdx.x < kTopkRows && mask_ptr != nullptr && e0 + threadIdx.x < n) {
-        const int64_t uu = qu[e0 + threadIdx.x];
-        int64_t lo = mask_ptr[uu], hi = mask_ptr[uu + 1];
-        cend = hi;
-        while (lo < hi) {
-            const int64_t mid = (lo + hi) >> 1;
-            if ((int64_t)mask_idx[mid] < c0) lo = mid + 1; else hi = mid;
-        }
-        cur = lo;
-    }
-    const float *arow = ue + (wave * 32 + col) * ldw + half;
-    const float *brow = it + col * ldw + half;
-    for (int64_t j0 = c0; j0 < c1; j0 += kTopkTileG) {
-        __syncthreads();
-        for (int idx = threadIdx.x; idx < kTopkTileG * D; idx += kBlock) {
-            const int r = idx / D, kk = idx - r * D;
-            it[r * ldw + kk] = (j0 + r < n_items) ? I[(j0 + r) * (int64_t)D + kk] : 0.f;
-        }
-        if (threadIdx.x < kTopkRows) {
-            unsigned m = 0;
-            while (cur < cend && (int64_t)mask_idx[cur] < j0 + kTopkTileG) {
-                if ((int64_t)mask_idx[cur] >= j0) m |= 1u << (unsigned)(mask_idx[cur] - j0);
-                ++cur;
-            }
-            rowmask[threadIdx.x] = m;
-        }
-        __syncthreads();
-        tk_f32x16 acc[1];
-        acc[0] = tk_f32x16{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-        for (int k0 = 0; k0 < D; k0 += 2) acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(arow[k0], brow[k0], acc[0], 0, 0, 0);
-        topk_absorb<1, E>(w, acc, j0, false, n_items,
-                          [&](int, int row) { return ((rowmask[wave * 32 + row] >> col) & 1u) != 0; });
-    }
+    unsigned *thr_s = score_lds_side(D);                                // [kScoreRows]
+    int *cnt_s = reinterpret_cast<int *>(thr_s + kScoreRows);           // [kScoreRows]
+    const TopkRows w = topk_rows<E>(ws, nc, k, kScoreTileG, n, thr_s, cnt_s);
+    score_scan_lds(U, I, D, n_items, qu, n, mask_ptr, mask_idx, (int64_t)blockIdx.y * chunk, chunk,
+                   [&](const auto &acc, int64_t j0, bool plain, auto masked) {
+                       topk_absorb<E>(w, acc, j0, plain, n_items, masked);
+                   });
     wave_sync();
     topk_merge_rows<E>(w, 0);
 }
@@ -437,10 +285,8 @@ __global__ __launch_bounds__(kBlock) void topk_merge_kernel(const u64 *__restric
     }
 }
 
-static inline bool topk_rega_d(int32_t D) { return D == 64 || D == 32 || D == 16 || D == 8; }
-
 // LDS-operand kernel: (128 + 32) rows of D + 1 floats, 128 mask words, 128 thresholds, 128 counts
-static inline size_t topk_lds_generic(int32_t D) { return ((size_t)(kTopkRows + kTopkTileG) * (D + 1) + 3 * kTopkRows) * 4; }
+static inline size_t topk_lds_generic(int32_t D) { return score_lds_bytes(D, 3); }
 
 // Chunks per call: enough workgroups to fill the chip in whole rounds (a workgroup runs for the length of its chunk, so a
 // grid of 1.02 rounds takes 2), fewer when that does not pay 2 % (every chunk adds candidates and a list to merge).
@@ -450,7 +296,7 @@ static inline int64_t topk_max_chunks(int64_t n_items) {
 }
 
 static inline int64_t topk_chunks(int64_t n, int64_t n_items) {
-    const int64_t rb = (n + kTopkRows - 1) / kTopkRows;
+    const int64_t rb = (n + kScoreRows - 1) / kScoreRows;
     int64_t cap = topk_max_chunks(n_items);
     const int64_t wg_cap = rb > kTopkWgCap ? 1 : kTopkWgCap / rb;
     if (cap > wg_cap) cap = wg_cap;
@@ -475,7 +321,7 @@ extern "C" {
 
 int32_t wr_topk_supported(int32_t D, int32_t k) {
     if (k < 1 || k > 256 || D < 4 || D % 4 != 0) return 0;
-    return (topk_rega_d(D) || topk_lds_generic(D) <= 160 * 1024) ? 1 : 0;
+    return (score_rega_d(D) || topk_lds_generic(D) <= kLdsPerWorkgroup) ? 1 : 0;
 }
 
 int64_t wr_topk_workspace_bytes(int64_t n, int64_t n_items, int32_t D, int32_t k) {
@@ -486,9 +332,9 @@ int64_t wr_topk_workspace_bytes(int64_t n, int64_t n_items, int32_t D, int32_t k
     }
     // an upper bound of what topk_chunks picks that never decreases in n, n_items or k:
     // rb * nc <= min(rb * max_chunks(n_items), max(rb, kTopkWgCap)) regions of 128 rows
-    const int64_t rb = (n + kTopkRows - 1) / kTopkRows;
+    const int64_t rb = (n + kScoreRows - 1) / kScoreRows;
     const int64_t a = rb * topk_max_chunks(n_items), b = rb > kTopkWgCap ? rb : kTopkWgCap;
-    const int64_t regions = (a < b ? a : b) * kTopkRows;
+    const int64_t regions = (a < b ? a : b) * kScoreRows;
     return regions * topk_region(k) * 8 + 256;
 }
 
@@ -513,21 +359,20 @@ int32_t wr_topk_recommend(const float *user_mat, int64_t n_user_rows, const floa
     if (n == 0) return WR_OK;
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     u64 *ws = reinterpret_cast<u64 *>(workspace);
-    const int64_t tiles = (n_items + kTopkTile - 1) / kTopkTile;
+    const int64_t tiles = (n_items + kScoreTile - 1) / kScoreTile;
     int64_t nc = topk_chunks(n, n_items);
-    const int64_t chunk = (tiles + nc - 1) / nc * kTopkTile;     // whole tiles of both kernels
+    const int64_t chunk = (tiles + nc - 1) / nc * kScoreTile;     // whole tiles of both kernels
     nc = (n_items + chunk - 1) / chunk;
-    const dim3 grid((unsigned)((n + kTopkRows - 1) / kTopkRows), (unsigned)nc);
+    const dim3 grid((unsigned)((n + kScoreRows - 1) / kScoreRows), (unsigned)nc);
     const bool big = k > 128;
     const int nci = (int)nc;
-    if (topk_rega_d(D)) {
+    if (score_rega_d(D)) {
 #define WR_TOPK_REGA(KS_, E_)                                                                                            \
     hipLaunchKernelGGL((topk_scan_kernel_rega<KS_, E_>), grid, dim3(kBlock), 0, stream, user_mat, item_tab, n_items, \
                        query_user, n, mask_ptr, mask_idx, k, chunk, nci, ws)
-        if (D == 64) { if (big) WR_TOPK_REGA(32, 8); else WR_TOPK_REGA(32, 4); }
-        else if (D == 32) { if (big) WR_TOPK_REGA(16, 8); else WR_TOPK_REGA(16, 4); }
-        else if (D == 16) { if (big) WR_TOPK_REGA(8, 8); else WR_TOPK_REGA(8, 4); }
-        else { if (big) WR_TOPK_REGA(4, 8); else WR_TOPK_REGA(4, 4); }
+#define WR_TOPK_REGA_K(KS_) do { if (big) WR_TOPK_REGA(KS_, 8); else WR_TOPK_REGA(KS_, 4); } while (0)
+        WR_DISPATCH_KS(D, 4, 32, WR_TOPK_REGA_K);
+#undef WR_TOPK_REGA_K
 #undef WR_TOPK_REGA
     } else {
         const size_t lds = topk_lds_generic(D);
