@@ -1019,14 +1019,6 @@ __global__ __launch_bounds__(kBlock) void bprmf_item_hot_combine(float *__restri
 }
 
 // ----------------------------------------------------------------------------------------------- host side
-static inline int teams_per_block(int D) {
-    if (D >= 64) return kBlock / 16;
-    if (D == 32) return kBlock / 8;
-    if (D == 16) return kBlock / 4;
-    if (D == 8) return kBlock / 2;
-    if (D == 4) return kBlock / 1;
-    return kBlock / 16;
-}
 static inline int64_t n_blocks_for(int64_t n_teams, int D) {
     const int tpb = teams_per_block(D);
     return (n_teams + tpb - 1) / tpb;
@@ -1053,16 +1045,13 @@ struct HotBatch {
     HotSide item, user;
 };
 
-static inline HotBatch hot_of(const wr_hot_runs *hot, int64_t batch) {
-    HotBatch h{{nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0}, {nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0}};
+// launch form of ONE batch's hot runs: `hot` is already offset to the batch (PlanBatch::hot(), hot_at_batch), or NULL
+static inline HotBatch hot_launch_form(const wr_hot_runs *hot) {
+    HotBatch h{};
     if (hot == nullptr || hot->counts_host == nullptr) return h;
-    const int32_t *c = hot->counts_host + 4 * batch;
-    h.item = HotSide{hot->piece_q + batch * hot->cap_pieces, hot->piece_len + batch * hot->cap_pieces,
-                     hot->run_q + batch * hot->cap_runs, hot->run_first + batch * hot->cap_runs,
-                     hot->run_np + batch * hot->cap_runs, c[0], c[1]};
-    h.user = HotSide{hot->u_piece_q + batch * hot->cap_u_pieces, hot->u_piece_len + batch * hot->cap_u_pieces,
-                     hot->u_run_q + batch * hot->cap_u_runs, hot->u_run_first + batch * hot->cap_u_runs,
-                     hot->u_run_np + batch * hot->cap_u_runs, c[2], c[3]};
+    const int32_t *c = hot->counts_host;
+    h.item = HotSide{hot->piece_q, hot->piece_len, hot->run_q, hot->run_first, hot->run_np, c[0], c[1]};
+    h.user = HotSide{hot->u_piece_q, hot->u_piece_len, hot->u_run_q, hot->u_run_first, hot->u_run_np, c[2], c[3]};
     return h;
 }
 
@@ -1085,17 +1074,46 @@ static inline StepWs carve_step_ws(void *workspace, int64_t B, int32_t D) {
     return w;
 }
 
+// One step of one batch (host only: the kernels receive these values one by one).  Fill it by field name from a
+// zero-initialised value — step_args() sets what every step has — so a call site names exactly what it uses.
+struct StepArgs {
+    float *U, *I;
+    int32_t D, step_id;                       // rows of the batch get step_id in stamp_u / stamp_i
+    const int32_t *tu, *tp, *tn, *oc_item, *oc_src;
+    int64_t B, ws_batch;                      // ws_batch: batch size the workspace was sized for (0: B)
+    float lr, l2, denom;                      // denom: divisor of the loss mean (0: B — a single-device step)
+    float *gradU, *gradI, *loss_out;          // MODE 1 / 2: gradient tables or slots
+    int32_t *stamp_u, *stamp_i;
+    void *workspace;
+    void *const *events;                      // four timing hooks, or NULL
+    HotBatch hot;
+    AdamArgs ad;
+    hipStream_t stream;
+};
+
+static inline StepArgs step_args(const TablePair &t, const PlanBatch &pb, int64_t ws_batch, void *workspace, void *stream) {
+    StepArgs a{};
+    a.U = t.U; a.I = t.I; a.D = t.D;
+    a.tu = pb.tu; a.tp = pb.tp; a.tn = pb.tn; a.oc_item = pb.oc_item; a.oc_src = pb.oc_src;
+    a.B = pb.Bk;
+    a.hot = hot_launch_form(pb.hot());
+    a.workspace = workspace; a.ws_batch = ws_batch;
+    a.stream = reinterpret_cast<hipStream_t>(stream);
+    return a;
+}
+
 template <int MODE>
-static int32_t launch_step(float *U, float *I, int32_t D, const int32_t *tu, const int32_t *tp, const int32_t *tn,
-                           const int32_t *oc_item, const int32_t *oc_src, int64_t B, float lr, float l2, float *gradU,
-                           float *gradI, int32_t *stamp_u, int32_t *stamp_i, int32_t step_id, float *loss_out,
-                           void *workspace, hipStream_t stream, void *const *events = nullptr, float denom = 0.f,
-                           HotBatch hot = HotBatch{{nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0},
-                                                   {nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0}},
-                           int64_t ws_batch = 0, AdamArgs ad = AdamArgs{}) {
-    if (denom <= 0.f) denom = (float)B;  // single-device step: mean over this batch
-    if (ws_batch <= 0) ws_batch = B;     // the workspace was sized for the plan's batch size (>= this batch)
-    const StepWs w = carve_step_ws(workspace, ws_batch, D);
+static int32_t launch_step(const StepArgs &a) {
+    float *const U = a.U, *const I = a.I, *const gradU = a.gradU, *const gradI = a.gradI, *const loss_out = a.loss_out;
+    const int32_t *const tu = a.tu, *const tp = a.tp, *const tn = a.tn, *const oc_item = a.oc_item, *const oc_src = a.oc_src;
+    int32_t *const stamp_u = a.stamp_u, *const stamp_i = a.stamp_i;
+    const int32_t D = a.D, step_id = a.step_id;
+    const int64_t B = a.B, ws_batch = a.ws_batch > 0 ? a.ws_batch : B;
+    const float lr = a.lr, l2 = a.l2, denom = a.denom > 0.f ? a.denom : (float)B;
+    const HotBatch &hot = a.hot;
+    const AdamArgs &ad = a.ad;
+    const hipStream_t stream = a.stream;
+    const StepWs w = carve_step_ws(a.workspace, ws_batch, D);
     const dim3 block(kBlock);
     const bool have_hot = hot.item.n_runs > 0 && hot.item.n_pieces > 0;
     const bool have_hot_u = hot.user.n_runs > 0 && hot.user.n_pieces > 0;
@@ -1113,7 +1131,7 @@ static int32_t launch_step(float *U, float *I, int32_t D, const int32_t *tu, con
     // Timing hooks, four events per step, any of them NULL: [0] / [1] start of the first and stop of the last kernel of the
     // user phase, [2] / [3] the same for the item phase.  They are attached to the dispatches (hipExtLaunchKernelGGL: the
     // events carry the kernel's own start / end timestamps, the ones rocprofv3 reports); no marker packet is queued.
-    auto ev = [&](int j) { return events ? reinterpret_cast<hipEvent_t>(events[j]) : (hipEvent_t) nullptr; };
+    auto ev = [&](int j) { return a.events ? reinterpret_cast<hipEvent_t>(a.events[j]) : (hipEvent_t) nullptr; };
     const hipEvent_t none = nullptr;
 #define WR_LAUNCH(kernel_, grid_, lds_, start_, stop_, ...)                                                               \
     do {                                                                                                                  \
@@ -1304,26 +1322,39 @@ __global__ __launch_bounds__(kBlock, NV == 1 ? (MODE == 4 ? WR_ADAM_WAVES : WR_U
 #define WR_CHAIN_TILE 64
 #endif
 
-static inline bool chain_shape_ok(const float *U, const float *I, int32_t D) {
-    return (D * 4) % 128 == 0 && (reinterpret_cast<uintptr_t>(U) & 127u) == 0 && (reinterpret_cast<uintptr_t>(I) & 127u) == 0;
-}
+// A range of chained steps (host only), filled by field name from a zero-initialised value.
+struct ChainArgs {
+    TablePair tabs;
+    PlanSpan plan;
+    BatchRange range;
+    float lr, l2, *loss_out;
+    const int32_t *tdef, *def_q, *def_count_host;   // the plan's deferred marks (wr_overlap.hip)
+    int64_t def_cap, def_limit, sync_words, adam_step0;
+    void *workspace;
+    uint32_t *sync;
+    void *const *events;                            // four timing hooks per step, or NULL
+    int n_cu;
+    AdamArgs ad_base;                               // MODE 4: everything but the step number and its constants
+    hipStream_t stream;
+};
 
 template <int T, int NV, bool FULL, int MODE = 0>
-static int32_t launch_chain_steps(float *U, float *I, int32_t D, const int32_t *tu, const int32_t *tp, const int32_t *tn,
-                                  const int32_t *oc_item, const int32_t *oc_src, int64_t n_triplets, int64_t batch_size,
-                                  int64_t first_batch, int64_t n_batches, float lr, float *loss_out, const int32_t *tdef,
-                                  const int32_t *def_q, const int32_t *def_count_host, int64_t def_cap, int64_t def_limit,
-                                  void *workspace, uint32_t *sync, int64_t sync_words, hipStream_t stream,
-                                  void *const *events, int n_cu, float l2 = 0.f, AdamArgs ad_base = AdamArgs{},
-                                  int64_t adam_step0 = 0) {
+static int32_t launch_chain_steps(const ChainArgs &c) {
+    float *const U = c.tabs.U, *const I = c.tabs.I, *const loss_out = c.loss_out;
+    const int32_t D = c.tabs.D;
+    const int32_t *const oc_item = c.plan.oc_item, *const oc_src = c.plan.oc_src;
+    const int64_t batch_size = c.plan.batch_size, n_batches = c.range.n_batches, def_cap = c.def_cap;
+    const float lr = c.lr, l2 = c.l2;
+    uint32_t *const sync = c.sync;
+    const hipStream_t stream = c.stream;
     const int64_t ws_one = step_ws_bytes(batch_size, D);
     // Forward progress: only the deferred workgroups ever wait, and nothing they wait for waits itself — so it is enough
     // that they never fill the device: at most half a workgroup per CU of THIS device (a CPX partition or a smaller agent
     // has fewer CUs than a whole MI355X's 256), never more than kChainDefBlocks.  With no room for even one, every step
     // takes the two-launch form.
-    const int max_def_blocks = std::min(kChainDefBlocks, n_cu / 2);
-    const StepWs w2[2] = {carve_step_ws(workspace, batch_size, D),
-                          carve_step_ws(reinterpret_cast<char *>(workspace) + ws_one, batch_size, D)};
+    const int max_def_blocks = std::min(kChainDefBlocks, c.n_cu / 2);
+    const StepWs w2[2] = {carve_step_ws(c.workspace, batch_size, D),
+                          carve_step_ws(reinterpret_cast<char *>(c.workspace) + ws_one, batch_size, D)};
     const int64_t dwords = (batch_size + 31) / 32;
     constexpr int TEAMS = kBlock / T;
     // occurrences per item tile: 64 for plain SGD (128 / 256: 23.1 / 24.0 us against 23.2), 256 for the folded Adam step, whose
@@ -1332,10 +1363,10 @@ static int32_t launch_chain_steps(float *U, float *I, int32_t D, const int32_t *
     const dim3 block(kBlock);
     // MODE 4: the optimizer step of batch k of this call is adam_step0 + k; its constants are those of wr_adam_consts
     auto ad_of = [&](int64_t k) {
-        AdamArgs a = ad_base;
+        AdamArgs a = c.ad_base;
         if (MODE == 4) {
-            a.t = (int)(adam_step0 + k);
-            adam_step_consts(adam_step0 + k, lr, a.b1, a.b2, &a.step_size, &a.inv_bc2_sqrt);
+            a.t = (int)(c.adam_step0 + k);
+            adam_step_consts(c.adam_step0 + k, lr, a.b1, a.b2, &a.step_size, &a.inv_bc2_sqrt);
         }
         return a;
     };
@@ -1343,37 +1374,33 @@ static int32_t launch_chain_steps(float *U, float *I, int32_t D, const int32_t *
     // bytes); the sticky timeout word is the first of the buffer's last four words
     const int64_t n_ctr = n_batches * kChainStepWords;
     WR_HIP(hipMemsetAsync(sync, 0, (size_t)n_ctr * 4, stream));
-    uint32_t *timeout = sync + (sync_words - 4);
-    auto ev = [&](int64_t k, int j) { return events ? reinterpret_cast<hipEvent_t>(events[4 * k + j]) : (hipEvent_t) nullptr; };
+    uint32_t *timeout = sync + (c.sync_words - 4);
+    auto ev = [&](int64_t k, int j) { return c.events ? reinterpret_cast<hipEvent_t>(c.events[4 * k + j]) : (hipEvent_t) nullptr; };
     // the item phase of the previous step, not yet launched: its arrays and what its loss needs
     struct Pending { bool on; int64_t off, Bk; int n_partials; int64_t k; } pend{false, 0, 0, 0, 0};
     auto launch_item = [&](const Pending &q, hipEvent_t e0, hipEvent_t e1) -> int32_t {
         const StepWs &w = w2[q.k & 1];
         const dim3 gridB((unsigned)((2 * q.Bk + kItemTile - 1) / kItemTile));
         const AdamArgs ad = ad_of(q.k);
+#define WR_ITEM_ARGS                                                                                                        \
+    I, D, oc_item + 2 * q.off, oc_src + 2 * q.off, (int)(2 * q.Bk), w.Z, lr, l2, (float *)nullptr, (int *)nullptr, 0, w.partials, \
+        q.n_partials, (float)q.Bk, at_or_null(loss_out, q.k), 0, (const unsigned long long *)nullptr, (int)gridB.x,            \
+        (const int *)nullptr, (const int *)nullptr, (float *)nullptr, ad
         if (e0 != nullptr || e1 != nullptr)
-            hipExtLaunchKernelGGL((bprmf_item_phase<T, NV, FULL, MODE, false>), gridB, block, 0, stream, e0, e1, 0, I, D,
-                                  oc_item + 2 * q.off, oc_src + 2 * q.off, (int)(2 * q.Bk), w.Z, lr, l2, (float *)nullptr,
-                                  (int *)nullptr, 0, w.partials, q.n_partials, (float)q.Bk, loss_out ? loss_out + q.k : nullptr, 0,
-                                  (const unsigned long long *)nullptr, (int)gridB.x, (const int *)nullptr, (const int *)nullptr,
-                                  (float *)nullptr, ad);
+            hipExtLaunchKernelGGL((bprmf_item_phase<T, NV, FULL, MODE, false>), gridB, block, 0, stream, e0, e1, 0, WR_ITEM_ARGS);
         else
-            hipLaunchKernelGGL((bprmf_item_phase<T, NV, FULL, MODE, false>), gridB, block, 0, stream, I, D, oc_item + 2 * q.off,
-                               oc_src + 2 * q.off, (int)(2 * q.Bk), w.Z, lr, l2, (float *)nullptr, (int *)nullptr, 0, w.partials,
-                               q.n_partials, (float)q.Bk, loss_out ? loss_out + q.k : nullptr, 0,
-                               (const unsigned long long *)nullptr, (int)gridB.x, (const int *)nullptr, (const int *)nullptr,
-                               (float *)nullptr, ad);
+            hipLaunchKernelGGL((bprmf_item_phase<T, NV, FULL, MODE, false>), gridB, block, 0, stream, WR_ITEM_ARGS);
+#undef WR_ITEM_ARGS
         WR_LAUNCH_CHECK("bprmf_item_phase (chain)");
         return WR_OK;
     };
     for (int64_t k = 0; k < n_batches; ++k) {
-        const int64_t b = first_batch + k;
-        const int64_t off = b * batch_size;
-        const int64_t Bk = (off + batch_size <= n_triplets) ? batch_size : (n_triplets - off);
+        const PlanBatch pb = batch_at(c.plan, c.range.first_batch + k);
+        const int64_t b = pb.b, off = pb.off, Bk = pb.Bk;
         const StepWs &w = w2[k & 1];
         const int nA = (int)n_blocks_for(Bk, D);
-        const int n_def = (k == 0 || !pend.on) ? -1 : def_count_host[b];
-        const bool chained = pend.on && n_def >= 0 && n_def <= def_cap && n_def <= def_limit && max_def_blocks >= 1;
+        const int n_def = (k == 0 || !pend.on) ? -1 : c.def_count_host[b];
+        const bool chained = pend.on && n_def >= 0 && n_def <= def_cap && n_def <= c.def_limit && max_def_blocks >= 1;
         if (chained) {
             const int n_chunks = (WR_CHAIN_DBG & 16) ? 0 : (n_def + TEAMS - 1) / TEAMS;
             const int nD = n_chunks < max_def_blocks ? n_chunks : max_def_blocks;
@@ -1384,8 +1411,8 @@ static int32_t launch_chain_steps(float *U, float *I, int32_t D, const int32_t *
             hipEvent_t e0 = ev(k, 0), e1 = ev(k, 1);
 #define WR_CHAIN_ARGS                                                                                                       \
     U, I, D, oc_item + 2 * pend.off, oc_src + 2 * pend.off, (int)(2 * pend.Bk), wp.Z, wp.partials, pend.n_partials,           \
-        (float)pend.Bk, loss_out ? loss_out + pend.k : (float *)nullptr, nI, item_at, tu + off, tp + off, tn + off, (int)Bk, lr,  \
-        w.Z, w.partials, (float)Bk, tdef + b * dwords, def_q + b * def_cap, n_def, nA, def_at, nD, sync + k * kChainStepWords,   \
+        (float)pend.Bk, at_or_null(loss_out, pend.k), nI, item_at, pb.tu, pb.tp, pb.tn, (int)Bk, lr,        \
+        w.Z, w.partials, (float)Bk, c.tdef + b * dwords, c.def_q + b * def_cap, n_def, nA, def_at, nD, sync + k * kChainStepWords,   \
         timeout, l2, ad_of(pend.k), ad_of(k)
             if (e0 != nullptr || e1 != nullptr)
                 hipExtLaunchKernelGGL((bprmf_chain_step<T, NV, FULL, kTile, MODE>), grid, block, 0, stream, e0, e1, 0,
@@ -1403,7 +1430,7 @@ static int32_t launch_chain_steps(float *U, float *I, int32_t D, const int32_t *
             hipEvent_t e0 = ev(k, 0), e1 = ev(k, 1);
             const AdamArgs ad = ad_of(k);
 #define WR_PLAIN_ARGS                                                                                                       \
-    U, I, D, tu + off, tp + off, tn + off, (int)Bk, lr, l2, w.Z, w.partials, (float *)nullptr, (int *)nullptr,               \
+    U, I, D, pb.tu, pb.tp, pb.tn, (int)Bk, lr, l2, w.Z, w.partials, (float *)nullptr, (int *)nullptr,                     \
         (float *)nullptr, (int *)nullptr, 0, (float)Bk, ad, (const int *)nullptr, (const int *)nullptr, 0, (const int *)nullptr
             if (e0 != nullptr || e1 != nullptr)
                 hipExtLaunchKernelGGL((bprmf_user_phase<T, NV, FULL, MODE, 1, false, 0>), dim3((unsigned)nA), block, 0, stream, e0, e1,
@@ -1420,10 +1447,31 @@ static int32_t launch_chain_steps(float *U, float *I, int32_t D, const int32_t *
     return WR_OK;
 }
 
-static int32_t check_plan_args(const void *tu, const void *tp, const void *tn, const void *oc_item, const void *oc_src,
-                               int64_t B) {
-    WR_REQUIRE(tu && tp && tn && oc_item && oc_src, WR_E_NULL, "plan arrays must not be NULL");
-    WR_REQUIRE(B > 0 && B <= (int64_t(1) << 29), WR_E_SHAPE, "batch size %lld out of range (1..2^29)", (long long)B);
+static inline int32_t check_adam_tables(const TablePair &t, const float *m_u, const float *v_u, const float *m_i, const float *v_i) {
+    return check_tables({{t.U, t.n_users, "user_tab"}, {t.I, t.n_items, "item_tab"}, {m_u, t.n_users, "m_u"},
+                         {v_u, t.n_users, "v_u"}, {m_i, t.n_items, "m_i"}, {v_i, t.n_items, "v_i"}}, t.D);
+}
+
+// What wr_bprmf_run_sgd_chain (MODE 0) and wr_bprmf_run_adam_folded_chain (MODE 4) share once their tables, plan arrays and
+// pointers are checked: the remaining checks in the entries' order, the CU count and the dispatch on D.
+template <int MODE>
+static int32_t run_chain(const char *entry, ChainArgs &c, bool lines_ok, int64_t workspace_bytes, int64_t n_consts) {
+    const int64_t n_batches = c.range.n_batches;
+    int32_t rc;
+    if ((rc = check_whole_lines(entry, lines_ok, c.tabs.D)) != WR_OK) return rc;
+    if ((rc = check_batch_range(c.plan, c.range)) != WR_OK) return rc;
+    WR_REQUIRE(MODE != 4 || (c.adam_step0 >= 1 && c.adam_step0 + n_batches <= n_consts && c.adam_step0 + n_batches < INT32_MAX),
+               WR_E_RANGE, "adam steps [%lld,%lld) outside the consts table (%lld entries)", (long long)c.adam_step0,
+               (long long)(c.adam_step0 + n_batches), (long long)n_consts);
+    WR_REQUIRE(c.def_cap > 0 && c.def_limit >= 0, WR_E_RANGE, "bad deferred-run capacity");
+    if ((rc = check_workspace(entry, c.workspace, workspace_bytes, 2 * step_ws_bytes(c.plan.batch_size, c.tabs.D))) != WR_OK)
+        return rc;
+    if ((rc = check_sync_words(entry, c.sync, c.sync_words, n_batches * kChainStepWords + 4)) != WR_OK) return rc;
+    if (n_batches == 0) return WR_OK;
+    if ((rc = device_cu_count(&c.n_cu)) != WR_OK) return rc;
+#define WR_CALL_CHAIN(T_, NV_, FULL_) return launch_chain_steps<T_, NV_, FULL_, MODE>(c)
+    WR_DISPATCH_D(c.tabs.D, WR_CALL_CHAIN);
+#undef WR_CALL_CHAIN
     return WR_OK;
 }
 
@@ -1440,8 +1488,7 @@ int32_t wr_bpr_fwd(const float *user_tab, int64_t n_users, const float *item_tab
                    float *coef, float *loss, void *workspace, int64_t workspace_bytes, void *stream_) {
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     int32_t rc;
-    if ((rc = check_table(user_tab, n_users, D, "user_tab")) != WR_OK) return rc;
-    if ((rc = check_table(item_tab, n_items, D, "item_tab")) != WR_OK) return rc;
+    if ((rc = check_tables({{user_tab, n_users, "user_tab"}, {item_tab, n_items, "item_tab"}}, D)) != WR_OK) return rc;
     WR_REQUIRE(u && p && n, WR_E_NULL, "index arrays must not be NULL");
     WR_REQUIRE(B > 0 && B <= (int64_t(1) << 29), WR_E_SHAPE, "B=%lld out of range", (long long)B);
     WR_REQUIRE(loss != nullptr || pos_score || neg_score || coef, WR_E_NULL, "no output requested");
@@ -1469,49 +1516,45 @@ void wr_bprmf_hot_caps(int64_t batch_size, int32_t kind, int64_t *cap_pieces, in
     if (cap_runs) *cap_runs = hot_cap_runs(batch_size, kind ? 1 : 0);
 }
 
+// The single-step entries take one batch of B triplets: a plan of one batch.
+
 int32_t wr_bprmf_step_sgd(float *user_tab, int64_t n_users, float *item_tab, int64_t n_items, int32_t D,
                           const int32_t *tu, const int32_t *tp, const int32_t *tn, const int32_t *oc_item,
                           const int32_t *oc_src, int64_t B, float lr, float l2, int32_t *stamp_u, int32_t *stamp_i,
                           int32_t step_id, float *loss_out, const wr_hot_runs *hot, void *workspace,
-                          int64_t workspace_bytes, void *stream_) {
+                          int64_t workspace_bytes, void *stream) {
+    const TablePair tabs{user_tab, item_tab, n_users, n_items, D};
+    const PlanSpan plan{tu, tp, tn, oc_item, oc_src, B, B, hot};
     int32_t rc;
-    if ((rc = check_table(user_tab, n_users, D, "user_tab")) != WR_OK) return rc;
-    if ((rc = check_table(item_tab, n_items, D, "item_tab")) != WR_OK) return rc;
-    if ((rc = check_plan_args(tu, tp, tn, oc_item, oc_src, B)) != WR_OK) return rc;
+    if ((rc = check_tables(tabs)) != WR_OK) return rc;
+    if ((rc = check_plan_args(plan)) != WR_OK) return rc;
     WR_REQUIRE(l2 == 0.0f || (stamp_u && stamp_i), WR_E_NULL, "l2 != 0 needs stamp_u/stamp_i for the dense decay pass");
-    WR_REQUIRE(workspace && aligned16(workspace) && workspace_bytes >= step_ws_bytes(B, D), WR_E_WORKSPACE,
-               "wr_bprmf_step_sgd: workspace %lld B < %lld B", (long long)workspace_bytes, (long long)step_ws_bytes(B, D));
-    return launch_step<0>(user_tab, item_tab, D, tu, tp, tn, oc_item, oc_src, B, lr, l2, nullptr, nullptr, stamp_u,
-                          stamp_i, step_id, loss_out, workspace, reinterpret_cast<hipStream_t>(stream_), nullptr, 0.f,
-                          hot_of(hot, 0));
+    if ((rc = check_workspace("wr_bprmf_step_sgd", workspace, workspace_bytes, step_ws_bytes(B, D))) != WR_OK) return rc;
+    StepArgs a = step_args(tabs, batch_at(plan, 0), B, workspace, stream);
+    a.lr = lr; a.l2 = l2;
+    a.stamp_u = stamp_u; a.stamp_i = stamp_i; a.step_id = step_id;
+    a.loss_out = loss_out;
+    return launch_step<0>(a);
 }
 
 int32_t wr_bprmf_run_sgd(float *user_tab, int64_t n_users, float *item_tab, int64_t n_items, int32_t D,
                          const int32_t *tu, const int32_t *tp, const int32_t *tn, const int32_t *oc_item,
                          const int32_t *oc_src, int64_t n_triplets, int64_t batch_size, int64_t first_batch,
                          int64_t n_batches, float lr, float *loss_out, void *const *phase_events, const wr_hot_runs *hot,
-                         void *workspace, int64_t workspace_bytes, void *stream_) {
+                         void *workspace, int64_t workspace_bytes, void *stream) {
+    const TablePair tabs{user_tab, item_tab, n_users, n_items, D};
+    const PlanSpan plan{tu, tp, tn, oc_item, oc_src, n_triplets, batch_size, hot};
     int32_t rc;
-    if ((rc = check_table(user_tab, n_users, D, "user_tab")) != WR_OK) return rc;
-    if ((rc = check_table(item_tab, n_items, D, "item_tab")) != WR_OK) return rc;
-    if ((rc = check_plan_args(tu, tp, tn, oc_item, oc_src, batch_size)) != WR_OK) return rc;
-    WR_REQUIRE(n_triplets > 0 && first_batch >= 0 && n_batches >= 0, WR_E_SHAPE, "bad batch range");
-    const int64_t total_batches = (n_triplets + batch_size - 1) / batch_size;
-    WR_REQUIRE(first_batch + n_batches <= total_batches, WR_E_SHAPE, "batches [%lld,%lld) exceed the plan's %lld",
-               (long long)first_batch, (long long)(first_batch + n_batches), (long long)total_batches);
-    WR_REQUIRE(workspace && aligned16(workspace) && workspace_bytes >= step_ws_bytes(batch_size, D), WR_E_WORKSPACE,
-               "wr_bprmf_run_sgd: workspace %lld B < %lld B", (long long)workspace_bytes,
-               (long long)step_ws_bytes(batch_size, D));
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    if ((rc = check_tables(tabs)) != WR_OK) return rc;
+    if ((rc = check_plan_args(plan)) != WR_OK) return rc;
+    if ((rc = check_batch_range(plan, {first_batch, n_batches})) != WR_OK) return rc;
+    if ((rc = check_workspace("wr_bprmf_run_sgd", workspace, workspace_bytes, step_ws_bytes(batch_size, D))) != WR_OK) return rc;
     for (int64_t k = 0; k < n_batches; ++k) {
-        const int64_t b = first_batch + k;
-        const int64_t off = b * batch_size;
-        const int64_t Bk = (off + batch_size <= n_triplets) ? batch_size : (n_triplets - off);
-        rc = launch_step<0>(user_tab, item_tab, D, tu + off, tp + off, tn + off, oc_item + 2 * off, oc_src + 2 * off, Bk,
-                            lr, 0.0f, nullptr, nullptr, nullptr, nullptr, 0, loss_out ? loss_out + k : nullptr,
-                            workspace, stream, phase_events ? phase_events + 4 * k : nullptr, 0.f, hot_of(hot, b),
-                            batch_size);
-        if (rc != WR_OK) return rc;
+        StepArgs a = step_args(tabs, batch_at(plan, first_batch + k), batch_size, workspace, stream);
+        a.lr = lr;
+        a.loss_out = at_or_null(loss_out, k);
+        a.events = at_or_null(phase_events, 4 * k);
+        if ((rc = launch_step<0>(a)) != WR_OK) return rc;
     }
     return WR_OK;
 }
@@ -1520,42 +1563,41 @@ int32_t wr_bprmf_grads(const float *user_tab, int64_t n_users, const float *item
                        const int32_t *tu, const int32_t *tp, const int32_t *tn, const int32_t *oc_item,
                        const int32_t *oc_src, int64_t B, float *grad_u, float *grad_i, int32_t *stamp_u,
                        int32_t *stamp_i, int32_t step_id, float *loss_out, const wr_hot_runs *hot, void *workspace,
-                       int64_t workspace_bytes, void *stream_) {
-    int32_t rc;
-    if ((rc = check_table(user_tab, n_users, D, "user_tab")) != WR_OK) return rc;
-    if ((rc = check_table(item_tab, n_items, D, "item_tab")) != WR_OK) return rc;
-    if ((rc = check_table(grad_u, n_users, D, "grad_u")) != WR_OK) return rc;
-    if ((rc = check_table(grad_i, n_items, D, "grad_i")) != WR_OK) return rc;
-    if ((rc = check_plan_args(tu, tp, tn, oc_item, oc_src, B)) != WR_OK) return rc;
-    WR_REQUIRE(workspace && aligned16(workspace) && workspace_bytes >= step_ws_bytes(B, D), WR_E_WORKSPACE,
-               "wr_bprmf_grads: workspace %lld B < %lld B", (long long)workspace_bytes, (long long)step_ws_bytes(B, D));
+                       int64_t workspace_bytes, void *stream) {
     // MODE 1 never writes the tables; the const_cast only serves the shared kernel signature.
-    return launch_step<1>(const_cast<float *>(user_tab), const_cast<float *>(item_tab), D, tu, tp, tn, oc_item, oc_src, B,
-                          0.f, 0.f, grad_u, grad_i, stamp_u, stamp_i, step_id, loss_out, workspace,
-                          reinterpret_cast<hipStream_t>(stream_), nullptr, 0.f, hot_of(hot, 0));
+    const TablePair tabs{const_cast<float *>(user_tab), const_cast<float *>(item_tab), n_users, n_items, D};
+    const PlanSpan plan{tu, tp, tn, oc_item, oc_src, B, B, hot};
+    int32_t rc;
+    if ((rc = check_tables({{user_tab, n_users, "user_tab"}, {item_tab, n_items, "item_tab"}, {grad_u, n_users, "grad_u"},
+                            {grad_i, n_items, "grad_i"}}, D)) != WR_OK) return rc;
+    if ((rc = check_plan_args(plan)) != WR_OK) return rc;
+    if ((rc = check_workspace("wr_bprmf_grads", workspace, workspace_bytes, step_ws_bytes(B, D))) != WR_OK) return rc;
+    StepArgs a = step_args(tabs, batch_at(plan, 0), B, workspace, stream);
+    a.gradU = grad_u; a.gradI = grad_i;
+    a.stamp_u = stamp_u; a.stamp_i = stamp_i; a.step_id = step_id;
+    a.loss_out = loss_out;
+    return launch_step<1>(a);
 }
 
 int32_t wr_bprmf_step_adam(float *user_tab, int64_t n_users, float *item_tab, int64_t n_items, int32_t D, float *m_u,
                            float *v_u, float *m_i, float *v_i, int32_t *last_u, int32_t *last_i, const int32_t *tu,
                            const int32_t *tp, const int32_t *tn, const int32_t *oc_item, const int32_t *oc_src, int64_t B,
                            int64_t adam_step, float lr, float l2, float beta1, float beta2, float eps, float *loss_out,
-                           const wr_hot_runs *hot, void *workspace, int64_t workspace_bytes, void *stream_) {
+                           const wr_hot_runs *hot, void *workspace, int64_t workspace_bytes, void *stream) {
+    const TablePair tabs{user_tab, item_tab, n_users, n_items, D};
+    const PlanSpan plan{tu, tp, tn, oc_item, oc_src, B, B, hot};
     int32_t rc;
-    if ((rc = check_table(user_tab, n_users, D, "user_tab")) != WR_OK) return rc;
-    if ((rc = check_table(item_tab, n_items, D, "item_tab")) != WR_OK) return rc;
-    if ((rc = check_table(m_u, n_users, D, "m_u")) != WR_OK) return rc;
-    if ((rc = check_table(v_u, n_users, D, "v_u")) != WR_OK) return rc;
-    if ((rc = check_table(m_i, n_items, D, "m_i")) != WR_OK) return rc;
-    if ((rc = check_table(v_i, n_items, D, "v_i")) != WR_OK) return rc;
-    if ((rc = check_plan_args(tu, tp, tn, oc_item, oc_src, B)) != WR_OK) return rc;
+    if ((rc = check_adam_tables(tabs, m_u, v_u, m_i, v_i)) != WR_OK) return rc;
+    if ((rc = check_plan_args(plan)) != WR_OK) return rc;
     WR_REQUIRE(last_u != nullptr && last_i != nullptr, WR_E_NULL, "last_u / last_i is NULL");
     WR_REQUIRE(adam_step >= 1 && adam_step < INT32_MAX, WR_E_RANGE, "adam_step must be >= 1");
-    WR_REQUIRE(workspace && aligned16(workspace) && workspace_bytes >= step_ws_bytes(B, D), WR_E_WORKSPACE,
-               "wr_bprmf_step_adam: workspace %lld B < %lld B", (long long)workspace_bytes, (long long)step_ws_bytes(B, D));
-    AdamArgs ad{m_u, v_u, m_i, v_i, last_u, last_i, 0.f, 0.f, beta1, beta2, eps, l2, (int)adam_step, nullptr};
-    adam_step_consts(adam_step, lr, beta1, beta2, &ad.step_size, &ad.inv_bc2_sqrt);
-    return launch_step<3>(user_tab, item_tab, D, tu, tp, tn, oc_item, oc_src, B, lr, l2, nullptr, nullptr, nullptr, nullptr, 0,
-                          loss_out, workspace, reinterpret_cast<hipStream_t>(stream_), nullptr, 0.f, hot_of(hot, 0), 0, ad);
+    if ((rc = check_workspace("wr_bprmf_step_adam", workspace, workspace_bytes, step_ws_bytes(B, D))) != WR_OK) return rc;
+    StepArgs a = step_args(tabs, batch_at(plan, 0), B, workspace, stream);
+    a.lr = lr; a.l2 = l2;
+    a.loss_out = loss_out;
+    a.ad = AdamArgs{m_u, v_u, m_i, v_i, last_u, last_i, 0.f, 0.f, beta1, beta2, eps, l2, (int)adam_step, nullptr};
+    adam_step_consts(adam_step, lr, beta1, beta2, &a.ad.step_size, &a.ad.inv_bc2_sqrt);
+    return launch_step<3>(a);
 }
 
 int32_t wr_bprmf_step_adam_folded(float *user_tab, int64_t n_users, float *item_tab, int64_t n_items, int32_t D, float *m_u,
@@ -1563,24 +1605,22 @@ int32_t wr_bprmf_step_adam_folded(float *user_tab, int64_t n_users, float *item_
                                   const int32_t *tp, const int32_t *tn, const int32_t *oc_item, const int32_t *oc_src,
                                   int64_t B, int64_t adam_step, float lr, const float *consts, int64_t n_consts, float l2,
                                   float beta1, float beta2, float eps, float *loss_out, void *workspace,
-                                  int64_t workspace_bytes, void *stream_) {
+                                  int64_t workspace_bytes, void *stream) {
+    const TablePair tabs{user_tab, item_tab, n_users, n_items, D};
+    const PlanSpan plan{tu, tp, tn, oc_item, oc_src, B, B, nullptr};   // the folded step takes no batch with hot rows
     int32_t rc;
-    if ((rc = check_table(user_tab, n_users, D, "user_tab")) != WR_OK) return rc;
-    if ((rc = check_table(item_tab, n_items, D, "item_tab")) != WR_OK) return rc;
-    if ((rc = check_table(m_u, n_users, D, "m_u")) != WR_OK) return rc;
-    if ((rc = check_table(v_u, n_users, D, "v_u")) != WR_OK) return rc;
-    if ((rc = check_table(m_i, n_items, D, "m_i")) != WR_OK) return rc;
-    if ((rc = check_table(v_i, n_items, D, "v_i")) != WR_OK) return rc;
-    if ((rc = check_plan_args(tu, tp, tn, oc_item, oc_src, B)) != WR_OK) return rc;
+    if ((rc = check_adam_tables(tabs, m_u, v_u, m_i, v_i)) != WR_OK) return rc;
+    if ((rc = check_plan_args(plan)) != WR_OK) return rc;
     WR_REQUIRE(last_u != nullptr && last_i != nullptr && consts != nullptr, WR_E_NULL, "last_u / last_i / consts is NULL");
     WR_REQUIRE(adam_step >= 1 && adam_step < n_consts && adam_step < INT32_MAX, WR_E_RANGE,
                "adam_step %lld outside the consts table (%lld entries)", (long long)adam_step, (long long)n_consts);
-    WR_REQUIRE(workspace && aligned16(workspace) && workspace_bytes >= step_ws_bytes(B, D), WR_E_WORKSPACE,
-               "wr_bprmf_step_adam_folded: workspace %lld B < %lld B", (long long)workspace_bytes, (long long)step_ws_bytes(B, D));
-    AdamArgs ad{m_u, v_u, m_i, v_i, last_u, last_i, 0.f, 0.f, beta1, beta2, eps, l2, (int)adam_step, consts};
-    adam_step_consts(adam_step, lr, beta1, beta2, &ad.step_size, &ad.inv_bc2_sqrt);   // = consts[2t], consts[2t+1]
-    return launch_step<4>(user_tab, item_tab, D, tu, tp, tn, oc_item, oc_src, B, lr, l2, nullptr, nullptr, nullptr, nullptr, 0,
-                          loss_out, workspace, reinterpret_cast<hipStream_t>(stream_), nullptr, 0.f, hot_of(nullptr, 0), 0, ad);
+    if ((rc = check_workspace("wr_bprmf_step_adam_folded", workspace, workspace_bytes, step_ws_bytes(B, D))) != WR_OK) return rc;
+    StepArgs a = step_args(tabs, batch_at(plan, 0), B, workspace, stream);
+    a.lr = lr; a.l2 = l2;
+    a.loss_out = loss_out;
+    a.ad = AdamArgs{m_u, v_u, m_i, v_i, last_u, last_i, 0.f, 0.f, beta1, beta2, eps, l2, (int)adam_step, consts};
+    adam_step_consts(adam_step, lr, beta1, beta2, &a.ad.step_size, &a.ad.inv_bc2_sqrt);   // = consts[2t], consts[2t+1]
+    return launch_step<4>(a);
 }
 
 int32_t wr_bprmf_run_stateful(int32_t kind, float *user_tab, int64_t n_users, float *item_tab, int64_t n_items, int32_t D,
@@ -1588,43 +1628,28 @@ int32_t wr_bprmf_run_stateful(int32_t kind, float *user_tab, int64_t n_users, fl
                               const int32_t *tu, const int32_t *tp, const int32_t *tn, const int32_t *oc_item,
                               const int32_t *oc_src, int64_t n_triplets, int64_t batch_size, int64_t first_batch,
                               int64_t n_batches, int64_t step0, float lr, float rho, float eps, float *loss_out,
-                              const wr_hot_runs *hot, void *workspace, int64_t workspace_bytes, void *stream_) {
+                              const wr_hot_runs *hot, void *workspace, int64_t workspace_bytes, void *stream) {
+    const TablePair tabs{user_tab, item_tab, n_users, n_items, D};
+    const PlanSpan plan{tu, tp, tn, oc_item, oc_src, n_triplets, batch_size, hot};
     int32_t rc;
     WR_REQUIRE(kind == 1 || kind == 2, WR_E_RANGE, "kind must be 1 (Adagrad) or 2 (Adadelta)");
-    if ((rc = check_table(user_tab, n_users, D, "user_tab")) != WR_OK) return rc;
-    if ((rc = check_table(item_tab, n_items, D, "item_tab")) != WR_OK) return rc;
-    if ((rc = check_table(s1_u, n_users, D, "s1_u")) != WR_OK) return rc;
-    if ((rc = check_table(s1_i, n_items, D, "s1_i")) != WR_OK) return rc;
+    if ((rc = check_tables({{user_tab, n_users, "user_tab"}, {item_tab, n_items, "item_tab"}, {s1_u, n_users, "s1_u"},
+                            {s1_i, n_items, "s1_i"}}, D)) != WR_OK) return rc;
     if (kind == 2) {
-        if ((rc = check_table(s2_u, n_users, D, "s2_u")) != WR_OK) return rc;
-        if ((rc = check_table(s2_i, n_items, D, "s2_i")) != WR_OK) return rc;
+        if ((rc = check_tables({{s2_u, n_users, "s2_u"}, {s2_i, n_items, "s2_i"}}, D)) != WR_OK) return rc;
         WR_REQUIRE(last_u != nullptr && last_i != nullptr, WR_E_NULL, "Adadelta needs last_u / last_i");
     }
-    if ((rc = check_plan_args(tu, tp, tn, oc_item, oc_src, batch_size)) != WR_OK) return rc;
-    WR_REQUIRE(n_triplets > 0 && first_batch >= 0 && n_batches >= 0 && step0 >= 1 && step0 + n_batches < INT32_MAX, WR_E_SHAPE,
-               "bad batch / step range");
-    const int64_t total_batches = (n_triplets + batch_size - 1) / batch_size;
-    WR_REQUIRE(first_batch + n_batches <= total_batches, WR_E_SHAPE, "batches [%lld,%lld) exceed the plan's %lld",
-               (long long)first_batch, (long long)(first_batch + n_batches), (long long)total_batches);
-    WR_REQUIRE(workspace && aligned16(workspace) && workspace_bytes >= step_ws_bytes(batch_size, D), WR_E_WORKSPACE,
-               "wr_bprmf_run_stateful: workspace %lld B < %lld B", (long long)workspace_bytes,
-               (long long)step_ws_bytes(batch_size, D));
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    if ((rc = check_plan_args(plan)) != WR_OK) return rc;
+    if ((rc = check_batch_range(plan, {first_batch, n_batches}, step0 >= 1 && step0 + n_batches < INT32_MAX,
+                                "bad batch / step range")) != WR_OK) return rc;
+    if ((rc = check_workspace("wr_bprmf_run_stateful", workspace, workspace_bytes, step_ws_bytes(batch_size, D))) != WR_OK)
+        return rc;
     for (int64_t k = 0; k < n_batches; ++k) {
-        const int64_t b = first_batch + k;
-        const int64_t off = b * batch_size;
-        const int64_t Bk = (off + batch_size <= n_triplets) ? batch_size : (n_triplets - off);
-        AdamArgs ad{s1_u, s2_u, s1_i, s2_i, last_u, last_i, lr, 0.f, rho, 0.f, eps, 0.f, (int)(step0 + k), nullptr};
-        float *lo = loss_out ? loss_out + k : nullptr;
-        if (kind == 1)
-            rc = launch_step<5>(user_tab, item_tab, D, tu + off, tp + off, tn + off, oc_item + 2 * off, oc_src + 2 * off, Bk, lr,
-                                0.f, nullptr, nullptr, nullptr, nullptr, 0, lo, workspace, stream, nullptr, 0.f, hot_of(hot, b),
-                                batch_size, ad);
-        else
-            rc = launch_step<6>(user_tab, item_tab, D, tu + off, tp + off, tn + off, oc_item + 2 * off, oc_src + 2 * off, Bk, lr,
-                                0.f, nullptr, nullptr, nullptr, nullptr, 0, lo, workspace, stream, nullptr, 0.f, hot_of(hot, b),
-                                batch_size, ad);
-        if (rc != WR_OK) return rc;
+        StepArgs a = step_args(tabs, batch_at(plan, first_batch + k), batch_size, workspace, stream);
+        a.lr = lr;
+        a.loss_out = at_or_null(loss_out, k);
+        a.ad = AdamArgs{s1_u, s2_u, s1_i, s2_i, last_u, last_i, lr, 0.f, rho, 0.f, eps, 0.f, (int)(step0 + k), nullptr};
+        if ((rc = kind == 1 ? launch_step<5>(a) : launch_step<6>(a)) != WR_OK) return rc;
     }
     return WR_OK;
 }
@@ -1643,7 +1668,6 @@ int32_t wr_bprmf_run_stateful_bounded(int32_t kind, float *user_tab, int64_t n_u
     WR_REQUIRE(max_lag >= 1 && sweep_pos != nullptr && sweep_pos[0] >= 0 && sweep_pos[1] >= 0, WR_E_RANGE,
                "max_lag must be >= 1 and sweep_pos given");
     WR_REQUIRE(n_users > 0 && n_items > 0 && n_batches >= 0 && step0 >= 1, WR_E_SHAPE, "bad sizes");
-    const int64_t rows[2] = {(n_users + max_lag - 1) / max_lag, (n_items + max_lag - 1) / max_lag};
     float *s1[2] = {s1_u, s1_i}, *s2[2] = {s2_u, s2_i};
     int32_t *lasts[2] = {last_u, last_i};
     const int64_t n_rows[2] = {n_users, n_items};
@@ -1651,19 +1675,15 @@ int32_t wr_bprmf_run_stateful_bounded(int32_t kind, float *user_tab, int64_t n_u
         int32_t rc;
         const int64_t t = step0 + k;
         for (int side = 0; side < 2 && kind == 2 && t > 1; ++side) {
-            int64_t lo = sweep_pos[side] % n_rows[side], left = rows[side] < n_rows[side] ? rows[side] : n_rows[side];
-            while (left > 0) {
-                const int64_t c = left < n_rows[side] - lo ? left : n_rows[side] - lo;
-                if ((rc = wr_adadelta_decay_all(s1[side] + lo * (int64_t)D, s2[side] + lo * (int64_t)D, lasts[side] + lo, c, D,
-                                                t - 1, rho, stream)) != WR_OK) return rc;
-                lo = (lo + c) % n_rows[side];
-                left -= c;
-            }
-            sweep_pos[side] = lo;
+            rc = walk_window(window_rows(n_rows[side], max_lag), n_rows[side], &sweep_pos[side], [&](int64_t lo, int64_t c) {
+                return wr_adadelta_decay_all(s1[side] + lo * (int64_t)D, s2[side] + lo * (int64_t)D, lasts[side] + lo, c, D, t - 1,
+                                             rho, stream);
+            });
+            if (rc != WR_OK) return rc;
         }
         if ((rc = wr_bprmf_run_stateful(kind, user_tab, n_users, item_tab, n_items, D, s1_u, s2_u, s1_i, s2_i, last_u, last_i, tu,
                                         tp, tn, oc_item, oc_src, n_triplets, batch_size, first_batch + k, 1, t, lr, rho, eps,
-                                        loss_out ? loss_out + k : nullptr, hot, workspace, workspace_bytes, stream)) != WR_OK)
+                                        at_or_null(loss_out, k), hot, workspace, workspace_bytes, stream)) != WR_OK)
             return rc;
     }
     return WR_OK;
@@ -1673,27 +1693,27 @@ int32_t wr_bprmf_shard_step(float *user_shard, int64_t n_user_rows, float *item_
                             int32_t D, const int32_t *tu, const int32_t *tp, const int32_t *tn, const int32_t *oc_item,
                             const int32_t *oc_src, int64_t B, int64_t global_batch, float lr, float *grad_slots,
                             float *loss_partial, const wr_hot_runs *hot, void *workspace, int64_t workspace_bytes,
-                            void *stream_) {
+                            void *stream) {
+    const TablePair tabs{user_shard, item_rows, n_user_rows, n_rows, D};
+    const PlanSpan plan{tu, tp, tn, oc_item, oc_src, B, B, hot};
     int32_t rc;
-    if ((rc = check_table(user_shard, n_user_rows, D, "user_shard")) != WR_OK) return rc;
-    if ((rc = check_table(item_rows, n_rows, D, "item_rows")) != WR_OK) return rc;
+    if ((rc = check_tables(tabs, "user_shard", "item_rows")) != WR_OK) return rc;
     WR_REQUIRE(n_local_items >= 0 && n_local_items <= n_rows, WR_E_SHAPE, "n_local_items %lld outside [0, %lld]",
                (long long)n_local_items, (long long)n_rows);
     WR_REQUIRE(grad_slots != nullptr && aligned16(grad_slots), WR_E_NULL, "grad_slots is NULL or not 16-byte aligned");
-    if ((rc = check_plan_args(tu, tp, tn, oc_item, oc_src, B)) != WR_OK) return rc;
+    if ((rc = check_plan_args(plan)) != WR_OK) return rc;
     WR_REQUIRE(global_batch >= B, WR_E_SHAPE, "global_batch %lld < local batch %lld", (long long)global_batch, (long long)B);
-    WR_REQUIRE(workspace && aligned16(workspace) && workspace_bytes >= step_ws_bytes(B, D), WR_E_WORKSPACE,
-               "wr_bprmf_shard_step: workspace %lld B < %lld B", (long long)workspace_bytes, (long long)step_ws_bytes(B, D));
+    if ((rc = check_workspace("wr_bprmf_shard_step", workspace, workspace_bytes, step_ws_bytes(B, D))) != WR_OK) return rc;
     // MODE 2: rows below n_local_items are rewritten in place, the others only read (their gradients go to grad_slots)
-    AdamArgs ad{};
-    ad.t = (int)n_local_items;
-    return launch_step<2>(user_shard, item_rows, D, tu, tp, tn, oc_item, oc_src, B, lr, 0.f, nullptr,
-                          grad_slots, nullptr, nullptr, 0, loss_partial, workspace, reinterpret_cast<hipStream_t>(stream_),
-                          nullptr, (float)global_batch, hot_of(hot, 0), 0, ad);
+    StepArgs a = step_args(tabs, batch_at(plan, 0), B, workspace, stream);
+    a.lr = lr; a.denom = (float)global_batch;
+    a.gradI = grad_slots; a.ad.t = (int)n_local_items;
+    a.loss_out = loss_partial;
+    return launch_step<2>(a);
 }
 
 int32_t wr_bprmf_chain_supported(const float *user_tab, const float *item_tab, int32_t D) {
-    return (user_tab && item_tab && D >= 4 && D <= 1024 && D % 4 == 0 && chain_shape_ok(user_tab, item_tab, D)) ? 1 : 0;
+    return (user_tab && item_tab && D >= 4 && D <= 1024 && D % 4 == 0 && whole_lines(user_tab, item_tab, D)) ? 1 : 0;
 }
 
 int64_t wr_bprmf_chain_sync_words(int64_t n_batches) { return n_batches < 0 ? WR_E_SHAPE : n_batches * kChainStepWords + 4; }
@@ -1703,43 +1723,21 @@ int32_t wr_bprmf_run_sgd_chain(float *user_tab, int64_t n_users, float *item_tab
                                const int32_t *oc_src, int64_t n_triplets, int64_t batch_size, int64_t first_batch,
                                int64_t n_batches, float lr, float *loss_out, const int32_t *tdef, const int32_t *def_q,
                                const int32_t *def_count_host, int64_t def_cap, int64_t def_limit, void *const *events,
-                               void *workspace, int64_t workspace_bytes, int32_t *sync, int64_t sync_words, void *stream_) {
+                               void *workspace, int64_t workspace_bytes, int32_t *sync, int64_t sync_words, void *stream) {
+    ChainArgs c{};
+    c.tabs = TablePair{user_tab, item_tab, n_users, n_items, D};
+    c.plan = PlanSpan{tu, tp, tn, oc_item, oc_src, n_triplets, batch_size, nullptr};
+    c.range = BatchRange{first_batch, n_batches};
+    c.lr = lr; c.loss_out = loss_out; c.events = events;
+    c.tdef = tdef; c.def_q = def_q; c.def_count_host = def_count_host; c.def_cap = def_cap; c.def_limit = def_limit;
+    c.workspace = workspace; c.sync = reinterpret_cast<uint32_t *>(sync); c.sync_words = sync_words;
+    c.stream = reinterpret_cast<hipStream_t>(stream);
     int32_t rc;
-    if ((rc = check_table(user_tab, n_users, D, "user_tab")) != WR_OK) return rc;
-    if ((rc = check_table(item_tab, n_items, D, "item_tab")) != WR_OK) return rc;
-    if ((rc = check_plan_args(tu, tp, tn, oc_item, oc_src, batch_size)) != WR_OK) return rc;
+    if ((rc = check_tables(c.tabs)) != WR_OK) return rc;
+    if ((rc = check_plan_args(c.plan)) != WR_OK) return rc;
     WR_REQUIRE(tdef && def_q && def_count_host && sync, WR_E_NULL, "chain marks / sync words must not be NULL");
-    WR_REQUIRE(chain_shape_ok(user_tab, item_tab, D), WR_E_ALIGN,
-               "wr_bprmf_run_sgd_chain: rows must be whole 128-B lines (D %% 32 == 0, tables 128-B aligned); D = %d", (int)D);
-    WR_REQUIRE(n_triplets > 0 && first_batch >= 0 && n_batches >= 0, WR_E_SHAPE, "bad batch range");
-    const int64_t total_batches = (n_triplets + batch_size - 1) / batch_size;
-    WR_REQUIRE(first_batch + n_batches <= total_batches, WR_E_SHAPE, "batches [%lld,%lld) exceed the plan's %lld",
-               (long long)first_batch, (long long)(first_batch + n_batches), (long long)total_batches);
-    WR_REQUIRE(def_cap > 0 && def_limit >= 0, WR_E_RANGE, "bad deferred-run capacity");
-    WR_REQUIRE(workspace && aligned16(workspace) && workspace_bytes >= 2 * step_ws_bytes(batch_size, D), WR_E_WORKSPACE,
-               "wr_bprmf_run_sgd_chain: workspace %lld B < %lld B", (long long)workspace_bytes,
-               (long long)(2 * step_ws_bytes(batch_size, D)));
-    WR_REQUIRE(aligned16(sync) && sync_words >= n_batches * kChainStepWords + 4, WR_E_WORKSPACE,
-               "wr_bprmf_run_sgd_chain: %lld sync words < %lld", (long long)sync_words,
-               (long long)(n_batches * kChainStepWords + 4));
-    if (n_batches == 0) return WR_OK;
-    static int n_cu = 0;
-    if (n_cu == 0) {
-        int dev = 0;
-        WR_HIP(hipGetDevice(&dev));
-        WR_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
-    }
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-#define WR_CALL_CHAIN(T_, NV_, FULL_)                                                                                      \
-    return launch_chain_steps<T_, NV_, FULL_>(user_tab, item_tab, D, tu, tp, tn, oc_item, oc_src, n_triplets, batch_size,   \
-                                              first_batch, n_batches, lr, loss_out, tdef, def_q, def_count_host, def_cap,  \
-                                              def_limit, workspace, reinterpret_cast<uint32_t *>(sync), sync_words, stream, \
-                                              events, n_cu)
-    WR_DISPATCH_D(D, WR_CALL_CHAIN);
-#undef WR_CALL_CHAIN
-    return WR_OK;
+    return run_chain<0>("wr_bprmf_run_sgd_chain", c, whole_lines(user_tab, item_tab, D), workspace_bytes, 0);
 }
-
 
 int32_t wr_bprmf_run_adam_folded_chain(float *user_tab, int64_t n_users, float *item_tab, int64_t n_items, int32_t D,
                                        float *m_u, float *v_u, float *m_i, float *v_i, int32_t *last_u, int32_t *last_i,
@@ -1749,51 +1747,25 @@ int32_t wr_bprmf_run_adam_folded_chain(float *user_tab, int64_t n_users, float *
                                        float l2, float beta1, float beta2, float eps, float *loss_out, const int32_t *tdef,
                                        const int32_t *def_q, const int32_t *def_count_host, int64_t def_cap, int64_t def_limit,
                                        void *workspace, int64_t workspace_bytes, int32_t *sync, int64_t sync_words,
-                                       void *stream_) {
+                                       void *stream) {
+    ChainArgs c{};
+    c.tabs = TablePair{user_tab, item_tab, n_users, n_items, D};
+    c.plan = PlanSpan{tu, tp, tn, oc_item, oc_src, n_triplets, batch_size, nullptr};
+    c.range = BatchRange{first_batch, n_batches};
+    c.lr = lr; c.l2 = l2; c.loss_out = loss_out;
+    c.tdef = tdef; c.def_q = def_q; c.def_count_host = def_count_host; c.def_cap = def_cap; c.def_limit = def_limit;
+    c.workspace = workspace; c.sync = reinterpret_cast<uint32_t *>(sync); c.sync_words = sync_words;
+    c.ad_base = AdamArgs{m_u, v_u, m_i, v_i, last_u, last_i, 0.f, 0.f, beta1, beta2, eps, l2, 0, consts};
+    c.adam_step0 = adam_step0;
+    c.stream = reinterpret_cast<hipStream_t>(stream);
     int32_t rc;
-    if ((rc = check_table(user_tab, n_users, D, "user_tab")) != WR_OK) return rc;
-    if ((rc = check_table(item_tab, n_items, D, "item_tab")) != WR_OK) return rc;
-    if ((rc = check_table(m_u, n_users, D, "m_u")) != WR_OK) return rc;
-    if ((rc = check_table(v_u, n_users, D, "v_u")) != WR_OK) return rc;
-    if ((rc = check_table(m_i, n_items, D, "m_i")) != WR_OK) return rc;
-    if ((rc = check_table(v_i, n_items, D, "v_i")) != WR_OK) return rc;
-    if ((rc = check_plan_args(tu, tp, tn, oc_item, oc_src, batch_size)) != WR_OK) return rc;
+    if ((rc = check_adam_tables(c.tabs, m_u, v_u, m_i, v_i)) != WR_OK) return rc;
+    if ((rc = check_plan_args(c.plan)) != WR_OK) return rc;
     WR_REQUIRE(last_u && last_i && consts && tdef && def_q && def_count_host && sync, WR_E_NULL,
                "last_u / last_i / consts / chain marks / sync words must not be NULL");
-    WR_REQUIRE(chain_shape_ok(user_tab, item_tab, D) && chain_shape_ok(m_u, m_i, D) && chain_shape_ok(v_u, v_i, D), WR_E_ALIGN,
-               "wr_bprmf_run_adam_folded_chain: rows must be whole 128-B lines (D %% 32 == 0, tables 128-B aligned); D = %d", (int)D);
-    WR_REQUIRE(n_triplets > 0 && first_batch >= 0 && n_batches >= 0, WR_E_SHAPE, "bad batch range");
-    const int64_t total_batches = (n_triplets + batch_size - 1) / batch_size;
-    WR_REQUIRE(first_batch + n_batches <= total_batches, WR_E_SHAPE, "batches [%lld,%lld) exceed the plan's %lld",
-               (long long)first_batch, (long long)(first_batch + n_batches), (long long)total_batches);
-    WR_REQUIRE(adam_step0 >= 1 && adam_step0 + n_batches <= n_consts && adam_step0 + n_batches < INT32_MAX, WR_E_RANGE,
-               "adam steps [%lld,%lld) outside the consts table (%lld entries)", (long long)adam_step0,
-               (long long)(adam_step0 + n_batches), (long long)n_consts);
-    WR_REQUIRE(def_cap > 0 && def_limit >= 0, WR_E_RANGE, "bad deferred-run capacity");
-    WR_REQUIRE(workspace && aligned16(workspace) && workspace_bytes >= 2 * step_ws_bytes(batch_size, D), WR_E_WORKSPACE,
-               "wr_bprmf_run_adam_folded_chain: workspace %lld B < %lld B", (long long)workspace_bytes,
-               (long long)(2 * step_ws_bytes(batch_size, D)));
-    WR_REQUIRE(aligned16(sync) && sync_words >= n_batches * kChainStepWords + 4, WR_E_WORKSPACE,
-               "wr_bprmf_run_adam_folded_chain: %lld sync words < %lld", (long long)sync_words,
-               (long long)(n_batches * kChainStepWords + 4));
-    if (n_batches == 0) return WR_OK;
-    static int n_cu = 0;
-    if (n_cu == 0) {
-        int dev = 0;
-        WR_HIP(hipGetDevice(&dev));
-        WR_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
-    }
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    const AdamArgs base{m_u, v_u, m_i, v_i, last_u, last_i, 0.f, 0.f, beta1, beta2, eps, l2, 0, consts};
-#define WR_CALL_ACHAIN(T_, NV_, FULL_)                                                                                       \
-    return launch_chain_steps<T_, NV_, FULL_, 4>(user_tab, item_tab, D, tu, tp, tn, oc_item, oc_src, n_triplets, batch_size,  \
-                                                 first_batch, n_batches, lr, loss_out, tdef, def_q, def_count_host, def_cap,   \
-                                                 def_limit, workspace, reinterpret_cast<uint32_t *>(sync), sync_words, stream, \
-                                                 nullptr, n_cu, l2, base, adam_step0)
-    WR_DISPATCH_D(D, WR_CALL_ACHAIN);
-#undef WR_CALL_ACHAIN
-    return WR_OK;
+    return run_chain<4>("wr_bprmf_run_adam_folded_chain", c,
+                        whole_lines(user_tab, item_tab, D) && whole_lines(m_u, m_i, D) && whole_lines(v_u, v_i, D), workspace_bytes,
+                        n_consts);
 }
-
 
 }  // extern "C"

@@ -4,6 +4,8 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <initializer_list>
+
 #include "whisprrec_hip.h"
 
 namespace wr {
@@ -199,11 +201,147 @@ __device__ __forceinline__ void bpr_terms(float pos, float neg, float batch_f, f
         else { CALL(16, 16, false); }                                               \
     } while (0)
 
+// teams of WR_DISPATCH_D's <T, ...> for D in one workgroup
+static inline int teams_per_block(int D) { return kBlock / (D >= 64 ? 16 : D == 32 ? 8 : D == 16 ? 4 : D == 8 ? 2 : D == 4 ? 1 : 16); }
+
 static inline int32_t check_table(const void *tab, int64_t n_rows, int32_t D, const char *name) {
     WR_REQUIRE(tab != nullptr, WR_E_NULL, "%s is NULL", name);
     WR_REQUIRE(n_rows > 0 && n_rows < (int64_t(1) << 31), WR_E_SHAPE, "%s: n_rows=%lld out of range", name, (long long)n_rows);
     WR_REQUIRE(D >= 4 && D <= 1024 && D % 4 == 0, WR_E_SHAPE, "%s: D=%d must be a multiple of 4 in [4,1024]", name, D);
     WR_REQUIRE(aligned16(tab), WR_E_ALIGN, "%s is not 16-byte aligned", name);
+    return WR_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ step entries (host)
+// What the wr_bprmf_* step entries (wr_bpr.hip, wr_lazy.hip, wr_group.hip) hand around: the two tables, the sorted plan, a
+// range of its batches — and the argument checks every entry's preamble is made of.  The texts are part of the interface
+// (tests/test_step_contract.py); `entry` is the exported name the message starts with.
+struct TablePair {
+    float *U, *I;
+    int64_t n_users, n_items;
+    int32_t D;
+};
+struct PlanSpan {
+    const int32_t *tu, *tp, *tn, *oc_item, *oc_src;
+    int64_t n_triplets, batch_size;
+    const wr_hot_runs *hot;   // per-batch arrays of the whole plan, or NULL
+};
+struct BatchRange { int64_t first_batch, n_batches; };
+struct PlanBatch {   // batch b of a plan: pointers already offset
+    int64_t b, off, Bk;
+    const int32_t *tu, *tp, *tn, *oc_item, *oc_src;
+    bool has_hot;
+    wr_hot_runs hot_runs;
+    const wr_hot_runs *hot() const { return has_hot ? &hot_runs : nullptr; }
+};
+
+template <typename P>
+static inline P *at_or_null(P *p, int64_t k) { return p ? p + k : nullptr; }   // element k of an optional array
+
+// every batch holds batch_size triplets but the plan's last one
+static inline int64_t batch_len(int64_t n_triplets, int64_t batch_size, int64_t b) {
+    const int64_t off = b * batch_size;
+    return (off + batch_size <= n_triplets) ? batch_size : (n_triplets - off);
+}
+
+static inline wr_hot_runs hot_at_batch(const wr_hot_runs *hot, int64_t b) {
+    wr_hot_runs h = *hot;
+    h.piece_q += b * hot->cap_pieces; h.piece_len += b * hot->cap_pieces;
+    h.run_q += b * hot->cap_runs; h.run_first += b * hot->cap_runs; h.run_np += b * hot->cap_runs;
+    h.u_piece_q += b * hot->cap_u_pieces; h.u_piece_len += b * hot->cap_u_pieces;
+    h.u_run_q += b * hot->cap_u_runs; h.u_run_first += b * hot->cap_u_runs; h.u_run_np += b * hot->cap_u_runs;
+    if (h.counts_host != nullptr) h.counts_host += 4 * b;
+    return h;
+}
+
+static inline PlanBatch batch_at(const PlanSpan &s, int64_t b) {
+    const int64_t off = b * s.batch_size;
+    PlanBatch pb{b, off, batch_len(s.n_triplets, s.batch_size, b), s.tu + off, s.tp + off, s.tn + off, s.oc_item + 2 * off,
+                 s.oc_src + 2 * off, s.hot != nullptr, {}};
+    if (pb.has_hot) pb.hot_runs = hot_at_batch(s.hot, b);
+    return pb;
+}
+
+struct NamedTable { const void *tab; int64_t n_rows; const char *name; };
+static inline int32_t check_tables(std::initializer_list<NamedTable> tabs, int32_t D) {
+    for (const NamedTable &t : tabs) {
+        const int32_t rc = check_table(t.tab, t.n_rows, D, t.name);
+        if (rc != WR_OK) return rc;
+    }
+    return WR_OK;
+}
+static inline int32_t check_tables(const TablePair &t, const char *user_name = "user_tab", const char *item_name = "item_tab") {
+    return check_tables({{t.U, t.n_users, user_name}, {t.I, t.n_items, item_name}}, t.D);
+}
+
+static inline int32_t check_plan_args(const PlanSpan &s) {
+    WR_REQUIRE(s.tu && s.tp && s.tn && s.oc_item && s.oc_src, WR_E_NULL, "plan arrays must not be NULL");
+    WR_REQUIRE(s.batch_size > 0 && s.batch_size <= (int64_t(1) << 29), WR_E_SHAPE, "batch size %lld out of range (1..2^29)",
+               (long long)s.batch_size);
+    return WR_OK;
+}
+
+static inline bool batch_range_sane(const PlanSpan &s, BatchRange r) {
+    return s.n_triplets > 0 && s.batch_size > 0 && r.first_batch >= 0 && r.n_batches >= 0;
+}
+static inline int32_t check_batch_range_fits(const PlanSpan &s, BatchRange r) {
+    const int64_t total_batches = (s.n_triplets + s.batch_size - 1) / s.batch_size;
+    WR_REQUIRE(r.first_batch + r.n_batches <= total_batches, WR_E_SHAPE, "batches [%lld,%lld) exceed the plan's %lld",
+               (long long)r.first_batch, (long long)(r.first_batch + r.n_batches), (long long)total_batches);
+    return WR_OK;
+}
+// `also`: what the entry requires of its step numbers in the same breath, under the text `what`
+static inline int32_t check_batch_range(const PlanSpan &s, BatchRange r, bool also = true, const char *what = "bad batch range") {
+    WR_REQUIRE(batch_range_sane(s, r) && also, WR_E_SHAPE, "%s", what);
+    return check_batch_range_fits(s, r);
+}
+
+static inline int32_t check_workspace(const char *entry, const void *workspace, int64_t bytes, int64_t need) {
+    WR_REQUIRE(workspace && aligned16(workspace) && bytes >= need, WR_E_WORKSPACE, "%s: workspace %lld B < %lld B", entry,
+               (long long)bytes, (long long)need);
+    return WR_OK;
+}
+static inline int32_t check_sync_words(const char *entry, const void *sync, int64_t words, int64_t need) {
+    WR_REQUIRE(aligned16(sync) && words >= need, WR_E_WORKSPACE, "%s: %lld sync words < %lld", entry, (long long)words,
+               (long long)need);
+    return WR_OK;
+}
+
+// rows handed from one workgroup to another inside a launch travel in whole 128-B lines
+static inline bool whole_lines(const float *a, const float *b, int32_t D) {
+    return (D * 4) % 128 == 0 && (reinterpret_cast<uintptr_t>(a) & 127u) == 0 && (reinterpret_cast<uintptr_t>(b) & 127u) == 0;
+}
+static inline int32_t check_whole_lines(const char *entry, bool ok, int32_t D) {
+    WR_REQUIRE(ok, WR_E_ALIGN, "%s: rows must be whole 128-B lines (D %% 32 == 0, tables 128-B aligned); D = %d", entry, (int)D);
+    return WR_OK;
+}
+
+// The rotating catch-up window of the bounded-lag loops: `rows` consecutive rows of a table of n_rows starting at *pos, in
+// up to two pieces across the wrap-around; f(lo, count) -> code handles a piece.  *pos moves on only when every piece did.
+static inline int64_t window_rows(int64_t n_rows, int64_t max_lag) { return (n_rows + max_lag - 1) / max_lag; }
+template <typename F>
+static inline int32_t walk_window(int64_t rows, int64_t n_rows, int64_t *pos, F &&f) {
+    int64_t lo = *pos % n_rows, left = rows < n_rows ? rows : n_rows;
+    while (left > 0) {
+        const int64_t c = left < n_rows - lo ? left : n_rows - lo;
+        const int32_t rc = f(lo, c);
+        if (rc != WR_OK) return rc;
+        lo = (lo + c) % n_rows;
+        left -= c;
+    }
+    *pos = lo;
+    return WR_OK;
+}
+
+// CUs of the current device, asked once (the in-launch hand-offs size their waiting workgroups by it)
+static inline int32_t device_cu_count(int *n_cu) {
+    static int cached = 0;
+    if (cached == 0) {
+        int dev = 0;
+        WR_HIP(hipGetDevice(&dev));
+        WR_HIP(hipDeviceGetAttribute(&cached, hipDeviceAttributeMultiprocessorCount, dev));
+    }
+    *n_cu = cached;
     return WR_OK;
 }
 

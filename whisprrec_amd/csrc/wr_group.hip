@@ -769,15 +769,9 @@ __global__ __launch_bounds__(kBlock, NV == 1 ? WR_GS_WAVES : 1) void bprmf_group
     if (threadIdx.x == 0) a.partials[slot] = sum;
 }
 
-static inline int gs_teams_per_block(int D) { return D >= 64 ? kBlock / 16 : (D == 32 ? kBlock / 8 : (D == 16 ? kBlock / 4 : (D == 8 ? kBlock / 2 : (D == 4 ? kBlock : kBlock / 16)))); }
-
 static inline int64_t gs_ws_one(int64_t B, int32_t D) {
-    const int64_t nA = (B + gs_teams_per_block(D) - 1) / gs_teams_per_block(D);
+    const int64_t nA = (B + teams_per_block(D) - 1) / teams_per_block(D);
     return 2 * align_up(B * (int64_t)D * 4, 256) + align_up((nA + 512) * 4, 256);
-}
-
-static inline bool gs_shape_ok(const float *U, const float *I, int32_t D) {
-    return (D * 4) % 128 == 0 && (reinterpret_cast<uintptr_t>(U) & 127u) == 0 && (reinterpret_cast<uintptr_t>(I) & 127u) == 0;
 }
 
 #ifndef WR_GS_TILES_AT
@@ -798,48 +792,63 @@ static inline bool gs_shape_ok(const float *U, const float *I, int32_t D) {
 #define WR_GS_NIT 1024
 #endif
 
+// A range of group steps (host only), filled by field name from a zero-initialised value.
+struct GroupRun {
+    TablePair tabs;
+    const int32_t *u, *p, *n, *plan;   // the triplets in batch order (no sort) and their group plan
+    int64_t n_triplets, batch_size, plan_words, workspace_bytes, sync_words;
+    BatchRange range;
+    float lr, *loss_out;
+    void *const *events;               // two timing hooks per step, or NULL
+    void *workspace;
+    uint32_t *sync;
+    int n_cu;                          // 0: ask the device
+    float *grad_slots;                 // row-sharded step only (GsArgs::Gs, nL) ...
+    int64_t n_local_items, global_batch;   // ... and the divisor of its loss mean (0: the batch's own size)
+    hipStream_t stream;
+};
+
 template <int T, int NV, bool FULL>
-static int32_t launch_group_steps(float *U, float *I, int32_t D, const int32_t *u, const int32_t *p, const int32_t *n,
-                                  int64_t n_triplets, const GroupLayout &L, const GpDev &G, int64_t first_batch,
-                                  int64_t n_batches, float lr, float *loss_out, void *workspace, uint32_t *sync,
-                                  int64_t sync_words, hipStream_t stream, void *const *events, int n_cu,
-                                  float *grad_slots = nullptr, int64_t n_local_items = 0, int64_t global_batch = 0) {
+static int32_t launch_group_steps(const GroupRun &g, const GroupLayout &L, const GpDev &G) {
+    const int32_t D = g.tabs.D;
+    const int64_t n_batches = g.range.n_batches, global_batch = g.global_batch;
+    uint32_t *const sync = g.sync;
     const int64_t B = L.B;
     const int64_t ws_one = gs_ws_one(B, D), zb = align_up(B * (int64_t)D * 4, 256);
-    char *ws = reinterpret_cast<char *>(workspace);
+    char *ws = reinterpret_cast<char *>(g.workspace);
     float *Zs[2] = {reinterpret_cast<float *>(ws), reinterpret_cast<float *>(ws + ws_one)};
     float *ZUs[2] = {reinterpret_cast<float *>(ws + zb), reinterpret_cast<float *>(ws + ws_one + zb)};
     float *Ps[2] = {reinterpret_cast<float *>(ws + 2 * zb), reinterpret_cast<float *>(ws + ws_one + 2 * zb)};
     constexpr int TEAMS = kBlock / T;
-    WR_HIP(hipMemsetAsync(sync, 0, (size_t)(n_batches * kGsStepWords) * 4, stream));
-    uint32_t *timeout = sync + (sync_words - 4);
+    WR_HIP(hipMemsetAsync(sync, 0, (size_t)(n_batches * kGsStepWords) * 4, g.stream));
+    uint32_t *timeout = sync + (g.sync_words - 4);
     // the workgroups that wait inside a launch (deferred triplets) must stay below the resident workgroup slots whatever
     // the device: at most a quarter of a workgroup per CU; nothing they wait for (the tiles) ever waits
     int nDS = WR_GS_NDS;
-    while (nDS > n_cu / 4 && nDS > 1) nDS >>= 1;
+    while (nDS > g.n_cu / 4 && nDS > 1) nDS >>= 1;
     auto batch_of = [&](int64_t b) {
         const int64_t off = b * B;
-        const int Bk = (int)((off + B <= n_triplets) ? B : (n_triplets - off));
-        return GsBatch{u + off, p + off, n + off, reinterpret_cast<const uint4 *>(G.flags + b * L.fw * 4),
+        const int Bk = (int)batch_len(g.n_triplets, B, b);
+        return GsBatch{g.u + off, g.p + off, g.n + off, reinterpret_cast<const uint4 *>(G.flags + b * L.fw * 4),
                        G.ul_row + b * L.R_u * (int64_t)L.cap_u, G.ul_src + b * L.R_u * (int64_t)L.cap_u, G.ucnt + b * L.R_u,
                        G.il_row + b * L.R_i * (int64_t)L.cap_i, G.il_src + b * L.R_i * (int64_t)L.cap_i, G.icnt + b * L.R_i,
                        Bk, L.R_u, L.R_i, L.cap_u, L.cap_i};
     };
-    auto ev = [&](int64_t k, int j) { return events ? reinterpret_cast<hipEvent_t>(events[2 * k + j]) : (hipEvent_t) nullptr; };
+    auto ev = [&](int64_t k, int j) { return g.events ? reinterpret_cast<hipEvent_t>(g.events[2 * k + j]) : (hipEvent_t) nullptr; };
     int n_partials_prev = 0;
     for (int64_t k = 0; k <= n_batches; ++k) {
         GsArgs a{};
-        a.U = U;
-        a.I = I;
+        a.U = g.tabs.U;
+        a.I = g.tabs.I;
         a.D = D;
-        a.lr = lr;
+        a.lr = g.lr;
         a.done = sync + (k < n_batches ? k : 0) * kGsStepWords;
         a.timeout = timeout;
-        a.Gs = grad_slots;
-        a.nL = (int)n_local_items;
+        a.Gs = g.grad_slots;
+        a.nL = (int)g.n_local_items;
         const bool have_cur = k < n_batches, have_prev = k > 0;
         if (have_cur) {
-            a.cur = batch_of(first_batch + k);
+            a.cur = batch_of(g.range.first_batch + k);
             a.Z = Zs[k & 1];
             a.ZU = ZUs[k & 1];
             a.partials = Ps[k & 1];
@@ -849,13 +858,13 @@ static int32_t launch_group_steps(float *U, float *I, int32_t D, const int32_t *
             a.chained = have_prev ? 1 : 0;
         }
         if (have_prev) {
-            a.prev = batch_of(first_batch + k - 1);
+            a.prev = batch_of(g.range.first_batch + k - 1);
             a.Zp = Zs[(k - 1) & 1];
             a.ZUp = ZUs[(k - 1) & 1];
             a.partials_prev = Ps[(k - 1) & 1];
             a.n_partials_prev = n_partials_prev;
             a.denom_prev = global_batch > 0 ? (float)global_batch : (float)a.prev.B;
-            a.loss_prev = loss_out ? loss_out + (k - 1) : nullptr;
+            a.loss_prev = at_or_null(g.loss_out, k - 1);
             // one tile (32 list entries) per workgroup where the lists are as long as uniform ids make them; longer lists
             // are walked in strides
             a.nIT = (int)std::min<int64_t>(WR_GS_NIT, (2 * B + kGsTile - 1) / kGsTile + L.R_i);
@@ -866,12 +875,37 @@ static int32_t launch_group_steps(float *U, float *I, int32_t D, const int32_t *
         const dim3 grid((unsigned)(a.nA + a.nIT + a.nUT + a.nDS));
         hipEvent_t e0 = have_cur ? ev(k, 0) : nullptr, e1 = have_cur ? ev(k, 1) : nullptr;
         if (e0 != nullptr || e1 != nullptr)
-            hipExtLaunchKernelGGL((bprmf_group_step<T, NV, FULL>), grid, dim3(kBlock), 0, stream, e0, e1, 0, a);
+            hipExtLaunchKernelGGL((bprmf_group_step<T, NV, FULL>), grid, dim3(kBlock), 0, g.stream, e0, e1, 0, a);
         else
-            hipLaunchKernelGGL((bprmf_group_step<T, NV, FULL>), grid, dim3(kBlock), 0, stream, a);
+            hipLaunchKernelGGL((bprmf_group_step<T, NV, FULL>), grid, dim3(kBlock), 0, g.stream, a);
         WR_LAUNCH_CHECK("bprmf_group_step");
         n_partials_prev = a.nA + a.nDS;
     }
+    return WR_OK;
+}
+
+// What wr_bprmf_run_sgd_group and wr_bprmf_shard_step_group share.  First: the tables are whole lines and the plan is one of
+// this shape (-> L).
+static int32_t check_group_plan(const char *entry, const GroupRun &g, GroupLayout &L) {
+    int32_t rc;
+    if ((rc = check_whole_lines(entry, whole_lines(g.tabs.U, g.tabs.I, g.tabs.D), g.tabs.D)) != WR_OK) return rc;
+    WR_REQUIRE(group_layout(g.n_triplets, g.batch_size, g.tabs.n_users, g.tabs.n_items, L), WR_E_RANGE,
+               "group plan not applicable to n=%lld, batch=%lld", (long long)g.n_triplets, (long long)g.batch_size);
+    WR_REQUIRE(g.plan_words >= L.total, WR_E_WORKSPACE, "group plan: %lld words < %lld", (long long)g.plan_words, (long long)L.total);
+    return WR_OK;
+}
+
+// Last: workspace and sync words (for sync_batches steps), then the launches of g.range.
+static int32_t run_group(const char *entry, GroupRun &g, const GroupLayout &L, int64_t sync_batches) {
+    int32_t rc;
+    if ((rc = check_workspace(entry, g.workspace, g.workspace_bytes, 2 * gs_ws_one(g.batch_size, g.tabs.D))) != WR_OK) return rc;
+    if ((rc = check_sync_words(entry, g.sync, g.sync_words, sync_batches * kGsStepWords + 4)) != WR_OK) return rc;
+    if (g.range.n_batches == 0) return WR_OK;
+    if (g.n_cu == 0 && (rc = device_cu_count(&g.n_cu)) != WR_OK) return rc;
+    const GpDev G = group_dev(const_cast<int32_t *>(g.plan), L);
+#define WR_CALL_GS(T_, NV_, FULL_) return launch_group_steps<T_, NV_, FULL_>(g, L, G)
+    WR_DISPATCH_D(g.tabs.D, WR_CALL_GS);
+#undef WR_CALL_GS
     return WR_OK;
 }
 
@@ -939,88 +973,64 @@ int64_t wr_bprmf_group_workspace_bytes(int64_t batch_size, int32_t D) { return 2
 int64_t wr_bprmf_group_sync_words(int64_t n_batches) { return n_batches < 0 ? WR_E_SHAPE : (n_batches + 1) * kGsStepWords + 4; }
 
 int32_t wr_bprmf_group_supported(const float *user_tab, const float *item_tab, int32_t D) {
-    return (user_tab && item_tab && D >= 4 && D <= 1024 && D % 4 == 0 && gs_shape_ok(user_tab, item_tab, D)) ? 1 : 0;
+    return (user_tab && item_tab && D >= 4 && D <= 1024 && D % 4 == 0 && whole_lines(user_tab, item_tab, D)) ? 1 : 0;
 }
 
 int32_t wr_bprmf_run_sgd_group(float *user_tab, int64_t n_users, float *item_tab, int64_t n_items, int32_t D,
                                const int32_t *u, const int32_t *p, const int32_t *n, int64_t n_triplets, int64_t batch_size,
                                const int32_t *plan, int64_t plan_words, int64_t first_batch, int64_t n_batches, float lr,
                                float *loss_out, void *const *events, void *workspace, int64_t workspace_bytes, int32_t *sync,
-                               int64_t sync_words, void *stream_) {
+                               int64_t sync_words, void *stream) {
+    GroupRun g{};
+    g.tabs = TablePair{user_tab, item_tab, n_users, n_items, D};
+    g.u = u; g.p = p; g.n = n; g.n_triplets = n_triplets; g.batch_size = batch_size;
+    g.plan = plan; g.plan_words = plan_words;
+    g.range = BatchRange{first_batch, n_batches};
+    g.lr = lr; g.loss_out = loss_out; g.events = events;
+    g.workspace = workspace; g.workspace_bytes = workspace_bytes;
+    g.sync = reinterpret_cast<uint32_t *>(sync); g.sync_words = sync_words;
+    g.stream = reinterpret_cast<hipStream_t>(stream);
     int32_t rc;
-    if ((rc = check_table(user_tab, n_users, D, "user_tab")) != WR_OK) return rc;
-    if ((rc = check_table(item_tab, n_items, D, "item_tab")) != WR_OK) return rc;
-    WR_REQUIRE(u && p && n && plan && sync, WR_E_NULL, "index arrays / plan / sync words must not be NULL");
-    WR_REQUIRE(gs_shape_ok(user_tab, item_tab, D), WR_E_ALIGN,
-               "wr_bprmf_run_sgd_group: rows must be whole 128-B lines (D %% 32 == 0, tables 128-B aligned); D = %d", (int)D);
     GroupLayout L;
-    WR_REQUIRE(group_layout(n_triplets, batch_size, n_users, n_items, L), WR_E_RANGE,
-               "group plan not applicable to n=%lld, batch=%lld", (long long)n_triplets, (long long)batch_size);
-    WR_REQUIRE(plan_words >= L.total, WR_E_WORKSPACE, "group plan: %lld words < %lld", (long long)plan_words, (long long)L.total);
+    if ((rc = check_tables(g.tabs)) != WR_OK) return rc;
+    WR_REQUIRE(u && p && n && plan && sync, WR_E_NULL, "index arrays / plan / sync words must not be NULL");
+    if ((rc = check_group_plan("wr_bprmf_run_sgd_group", g, L)) != WR_OK) return rc;
     WR_REQUIRE(first_batch >= 0 && n_batches >= 0 && first_batch + n_batches <= L.nb, WR_E_SHAPE,
                "batches [%lld,%lld) exceed the plan's %lld", (long long)first_batch, (long long)(first_batch + n_batches),
                (long long)L.nb);
-    WR_REQUIRE(workspace && aligned16(workspace) && workspace_bytes >= 2 * gs_ws_one(batch_size, D), WR_E_WORKSPACE,
-               "wr_bprmf_run_sgd_group: workspace %lld B < %lld B", (long long)workspace_bytes,
-               (long long)(2 * gs_ws_one(batch_size, D)));
-    WR_REQUIRE(aligned16(sync) && sync_words >= (n_batches + 1) * kGsStepWords + 4, WR_E_WORKSPACE,
-               "wr_bprmf_run_sgd_group: %lld sync words < %lld", (long long)sync_words,
-               (long long)((n_batches + 1) * kGsStepWords + 4));
-    if (n_batches == 0) return WR_OK;
-    static int n_cu = 0;
-    if (n_cu == 0) {
-        int dev = 0;
-        WR_HIP(hipGetDevice(&dev));
-        WR_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
-    }
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    const GpDev G = group_dev(const_cast<int32_t *>(plan), L);
-#define WR_CALL_GS(T_, NV_, FULL_)                                                                                          \
-    return launch_group_steps<T_, NV_, FULL_>(user_tab, item_tab, D, u, p, n, n_triplets, L, G, first_batch, n_batches, lr, \
-                                              loss_out, workspace, reinterpret_cast<uint32_t *>(sync), sync_words, stream,  \
-                                              events, n_cu)
-    WR_DISPATCH_D(D, WR_CALL_GS);
-#undef WR_CALL_GS
-    return WR_OK;
+    return run_group("wr_bprmf_run_sgd_group", g, L, n_batches + 1);
 }
 
 int32_t wr_bprmf_shard_step_group(float *user_shard, int64_t n_user_rows, float *item_ext, int64_t n_ext_rows,
                                   int64_t n_local_items, int32_t D, const int32_t *vu, const int32_t *vp, const int32_t *vn,
                                   int64_t n_triplets, int64_t batch_size, const int32_t *plan, int64_t plan_words, int64_t batch,
                                   int64_t global_batch, float lr, float *grad_slots, float *loss_partial, void *workspace,
-                                  int64_t workspace_bytes, int32_t *sync, int64_t sync_words, void *stream_) {
+                                  int64_t workspace_bytes, int32_t *sync, int64_t sync_words, void *stream) {
+    // one batch = the launch of its triplets + the launch of its own tiles (the tiles cannot ride in the next step's launch:
+    // the received rows and the gradient slots belong to THIS step's exchange)
+    GroupRun g{};
+    g.tabs = TablePair{user_shard, item_ext, n_user_rows, n_ext_rows, D};
+    g.u = vu; g.p = vp; g.n = vn; g.n_triplets = n_triplets; g.batch_size = batch_size;
+    g.plan = plan; g.plan_words = plan_words;
+    g.range = BatchRange{batch, 1};
+    g.lr = lr; g.loss_out = loss_partial;
+    g.workspace = workspace; g.workspace_bytes = workspace_bytes;
+    g.sync = reinterpret_cast<uint32_t *>(sync); g.sync_words = sync_words;
+    g.n_cu = 256;
+    g.grad_slots = grad_slots; g.n_local_items = n_local_items; g.global_batch = global_batch;
+    g.stream = reinterpret_cast<hipStream_t>(stream);
     int32_t rc;
-    if ((rc = check_table(user_shard, n_user_rows, D, "user_shard")) != WR_OK) return rc;
-    if ((rc = check_table(item_ext, n_ext_rows, D, "item_ext")) != WR_OK) return rc;
+    GroupLayout L;
+    if ((rc = check_tables(g.tabs, "user_shard", "item_ext")) != WR_OK) return rc;
     WR_REQUIRE(vu && vp && vn && plan && sync && grad_slots, WR_E_NULL, "index arrays / plan / sync words / grad_slots must not be NULL");
     WR_REQUIRE(aligned16(grad_slots), WR_E_ALIGN, "grad_slots is not 16-byte aligned");
     WR_REQUIRE(n_local_items >= 0 && n_local_items <= n_ext_rows, WR_E_SHAPE, "n_local_items %lld outside [0, %lld]",
                (long long)n_local_items, (long long)n_ext_rows);
-    WR_REQUIRE(gs_shape_ok(user_shard, item_ext, D), WR_E_ALIGN,
-               "wr_bprmf_shard_step_group: rows must be whole 128-B lines (D %% 32 == 0, tables 128-B aligned); D = %d", (int)D);
-    GroupLayout L;
-    WR_REQUIRE(group_layout(n_triplets, batch_size, n_user_rows, n_ext_rows, L), WR_E_RANGE,
-               "group plan not applicable to n=%lld, batch=%lld", (long long)n_triplets, (long long)batch_size);
-    WR_REQUIRE(plan_words >= L.total, WR_E_WORKSPACE, "group plan: %lld words < %lld", (long long)plan_words, (long long)L.total);
+    if ((rc = check_group_plan("wr_bprmf_shard_step_group", g, L)) != WR_OK) return rc;
     WR_REQUIRE(batch >= 0 && batch < L.nb, WR_E_SHAPE, "batch %lld outside the plan's %lld", (long long)batch, (long long)L.nb);
     WR_REQUIRE(global_batch >= batch_size, WR_E_SHAPE, "global_batch %lld < local batch %lld", (long long)global_batch,
                (long long)batch_size);
-    WR_REQUIRE(workspace && aligned16(workspace) && workspace_bytes >= 2 * gs_ws_one(batch_size, D), WR_E_WORKSPACE,
-               "wr_bprmf_shard_step_group: workspace %lld B < %lld B", (long long)workspace_bytes,
-               (long long)(2 * gs_ws_one(batch_size, D)));
-    WR_REQUIRE(aligned16(sync) && sync_words >= 2 * kGsStepWords + 4, WR_E_WORKSPACE, "wr_bprmf_shard_step_group: %lld sync words < %lld",
-               (long long)sync_words, (long long)(2 * kGsStepWords + 4));
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    const GpDev G = group_dev(const_cast<int32_t *>(plan), L);
-    // one batch = the launch of its triplets + the launch of its own tiles (the tiles cannot ride in the next step's launch:
-    // the received rows and the gradient slots belong to THIS step's exchange)
-#define WR_CALL_GSS(T_, NV_, FULL_)                                                                                        \
-    return launch_group_steps<T_, NV_, FULL_>(user_shard, item_ext, D, vu, vp, vn, n_triplets, L, G, batch, 1, lr,         \
-                                              loss_partial, workspace, reinterpret_cast<uint32_t *>(sync), sync_words,     \
-                                              stream, nullptr, 256, grad_slots, n_local_items, global_batch)
-    WR_DISPATCH_D(D, WR_CALL_GSS);
-#undef WR_CALL_GSS
-    return WR_OK;
+    return run_group("wr_bprmf_shard_step_group", g, L, 2);
 }
 
 }  // extern "C"

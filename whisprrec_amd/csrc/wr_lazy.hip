@@ -233,9 +233,8 @@ int32_t wr_adam_rows_lazy(float *tab, float *exp_avg, float *exp_avg_sq, int32_t
                           const int32_t *keys, int64_t n_keys, const float *grad, int64_t adam_step, const float *consts,
                           int64_t n_consts, float l2, float beta1, float beta2, float eps, void *stream_) {
     int32_t rc;
-    if ((rc = check_table(tab, n_rows, D, "tab")) != WR_OK) return rc;
-    if ((rc = check_table(exp_avg, n_rows, D, "exp_avg")) != WR_OK) return rc;
-    if ((rc = check_table(exp_avg_sq, n_rows, D, "exp_avg_sq")) != WR_OK) return rc;
+    if ((rc = check_tables({{tab, n_rows, "tab"}, {exp_avg, n_rows, "exp_avg"}, {exp_avg_sq, n_rows, "exp_avg_sq"}}, D)) != WR_OK)
+        return rc;
     WR_REQUIRE(last_step != nullptr && consts != nullptr, WR_E_NULL, "last_step / consts is NULL");
     WR_REQUIRE(adam_step >= 1 && adam_step < n_consts && adam_step < INT32_MAX, WR_E_RANGE,
                "adam_step %lld outside the consts table (%lld entries)", (long long)adam_step, (long long)n_consts);
@@ -256,9 +255,8 @@ int32_t wr_adam_catchup_all(float *tab, float *exp_avg, float *exp_avg_sq, int32
                             int64_t adam_step, const float *consts, int64_t n_consts, float l2, float beta1, float beta2,
                             float eps, void *stream_) {
     int32_t rc;
-    if ((rc = check_table(tab, n_rows, D, "tab")) != WR_OK) return rc;
-    if ((rc = check_table(exp_avg, n_rows, D, "exp_avg")) != WR_OK) return rc;
-    if ((rc = check_table(exp_avg_sq, n_rows, D, "exp_avg_sq")) != WR_OK) return rc;
+    if ((rc = check_tables({{tab, n_rows, "tab"}, {exp_avg, n_rows, "exp_avg"}, {exp_avg_sq, n_rows, "exp_avg_sq"}}, D)) != WR_OK)
+        return rc;
     WR_REQUIRE(last_step != nullptr && consts != nullptr, WR_E_NULL, "last_step / consts is NULL");
     WR_REQUIRE(adam_step >= 0 && adam_step < n_consts && adam_step < INT32_MAX, WR_E_RANGE,
                "adam_step %lld outside the consts table (%lld entries)", (long long)adam_step, (long long)n_consts);
@@ -304,19 +302,44 @@ int32_t wr_sgd_catchup_all(float *tab, int32_t *last_step, int64_t n_rows, int32
     return WR_OK;
 }
 
-static inline wr_hot_runs hot_at_batch(const wr_hot_runs *hot, int64_t b) {
-    wr_hot_runs h = *hot;
-    h.piece_q += b * hot->cap_pieces; h.piece_len += b * hot->cap_pieces;
-    h.run_q += b * hot->cap_runs; h.run_first += b * hot->cap_runs; h.run_np += b * hot->cap_runs;
-    h.u_piece_q += b * hot->cap_u_pieces; h.u_piece_len += b * hot->cap_u_pieces;
-    h.u_run_q += b * hot->cap_u_runs; h.u_run_first += b * hot->cap_u_runs; h.u_run_np += b * hot->cap_u_runs;
-    h.counts_host += 4 * b;
-    return h;
+// The run entries below check their ranges only: tables, plan arrays and workspace are checked by the per-step entries they
+// call (a call with n_batches == 0 succeeds whatever the tables are).
+static int32_t check_adam_steps(int64_t adam_step0, int64_t n_batches, int64_t n_consts) {
+    WR_REQUIRE(adam_step0 >= 1 && adam_step0 + n_batches <= n_consts, WR_E_RANGE,
+               "adam steps [%lld,%lld) outside the consts table (%lld entries)", (long long)adam_step0,
+               (long long)(adam_step0 + n_batches), (long long)n_consts);
+    return WR_OK;
 }
 
-// The per-batch sequence  catch-up rows -> fused step (gradients + Adam on the finished rows)  for n_batches consecutive
-// batches of a plan, issued from native code: at the reference's default batch size (2,048) a Python loop around the calls
-// costs about as much as the GPU work of a step.
+struct AdamRun {   // what the Adam loops hand to every step
+    TablePair tabs;
+    float *m_u, *v_u, *m_i, *v_i;
+    int32_t *last_u, *last_i;
+    float lr;
+    const float *consts;
+    int64_t n_consts;
+    float l2, beta1, beta2, eps;
+    void *workspace;
+    int64_t workspace_bytes;
+    void *stream;
+};
+
+// catch-up of the batch's rows to step t-1, then the fused step t (gradients + Adam on the finished rows)
+static int32_t adam_catchup_and_step(const AdamRun &r, const PlanBatch &pb, int64_t t, float *loss_out) {
+    const TablePair &T = r.tabs;
+    int32_t rc;
+    if ((rc = wr_adam_rows_lazy(T.U, r.m_u, r.v_u, r.last_u, T.n_users, T.D, pb.tu, pb.Bk, nullptr, t, r.consts, r.n_consts, r.l2,
+                                r.beta1, r.beta2, r.eps, r.stream)) != WR_OK) return rc;
+    if ((rc = wr_adam_rows_lazy(T.I, r.m_i, r.v_i, r.last_i, T.n_items, T.D, pb.oc_item, 2 * pb.Bk, nullptr, t, r.consts,
+                                r.n_consts, r.l2, r.beta1, r.beta2, r.eps, r.stream)) != WR_OK) return rc;
+    return wr_bprmf_step_adam(T.U, T.n_users, T.I, T.n_items, T.D, r.m_u, r.v_u, r.m_i, r.v_i, r.last_u, r.last_i, pb.tu, pb.tp,
+                              pb.tn, pb.oc_item, pb.oc_src, pb.Bk, t, r.lr, r.l2, r.beta1, r.beta2, r.eps, loss_out, pb.hot(),
+                              r.workspace, r.workspace_bytes, r.stream);
+}
+
+// The per-batch sequence  catch-up rows -> fused step  for n_batches consecutive batches of a plan, issued from native
+// code: at the reference's default batch size (2,048) a Python loop around the calls costs about as much as the GPU work of
+// a step.
 int32_t wr_bprmf_run_adam_lazy(float *user_tab, int64_t n_users, float *item_tab, int64_t n_items, int32_t D, float *m_u,
                                float *v_u, float *m_i, float *v_i, int32_t *last_u, int32_t *last_i, const int32_t *tu,
                                const int32_t *tp, const int32_t *tn, const int32_t *oc_item, const int32_t *oc_src,
@@ -324,29 +347,15 @@ int32_t wr_bprmf_run_adam_lazy(float *user_tab, int64_t n_users, float *item_tab
                                int64_t adam_step0, float lr, const float *consts, int64_t n_consts, float l2, float beta1,
                                float beta2, float eps, float *loss_out, const wr_hot_runs *hot, void *workspace,
                                int64_t workspace_bytes, void *stream) {
-    WR_REQUIRE(n_triplets > 0 && batch_size > 0 && first_batch >= 0 && n_batches >= 0, WR_E_SHAPE, "bad batch range");
-    const int64_t total_batches = (n_triplets + batch_size - 1) / batch_size;
-    WR_REQUIRE(first_batch + n_batches <= total_batches, WR_E_SHAPE, "batches [%lld,%lld) exceed the plan's %lld",
-               (long long)first_batch, (long long)(first_batch + n_batches), (long long)total_batches);
-    WR_REQUIRE(adam_step0 >= 1 && adam_step0 + n_batches <= n_consts, WR_E_RANGE,
-               "adam steps [%lld,%lld) outside the consts table (%lld entries)", (long long)adam_step0,
-               (long long)(adam_step0 + n_batches), (long long)n_consts);
-    for (int64_t k = 0; k < n_batches; ++k) {
-        const int64_t b = first_batch + k, off = b * batch_size;
-        const int64_t Bk = (off + batch_size <= n_triplets) ? batch_size : (n_triplets - off);
-        const int64_t t = adam_step0 + k;
-        int32_t rc;
-        wr_hot_runs hb;
-        if (hot != nullptr) hb = hot_at_batch(hot, b);
-        if ((rc = wr_adam_rows_lazy(user_tab, m_u, v_u, last_u, n_users, D, tu + off, Bk, nullptr, t, consts, n_consts, l2, beta1,
-                                    beta2, eps, stream)) != WR_OK) return rc;
-        if ((rc = wr_adam_rows_lazy(item_tab, m_i, v_i, last_i, n_items, D, oc_item + 2 * off, 2 * Bk, nullptr, t, consts,
-                                    n_consts, l2, beta1, beta2, eps, stream)) != WR_OK) return rc;
-        if ((rc = wr_bprmf_step_adam(user_tab, n_users, item_tab, n_items, D, m_u, v_u, m_i, v_i, last_u, last_i, tu + off,
-                                     tp + off, tn + off, oc_item + 2 * off, oc_src + 2 * off, Bk, t, lr, l2, beta1, beta2, eps,
-                                     loss_out ? loss_out + k : nullptr, hot ? &hb : nullptr, workspace, workspace_bytes,
-                                     stream)) != WR_OK) return rc;
-    }
+    const PlanSpan plan{tu, tp, tn, oc_item, oc_src, n_triplets, batch_size, hot};
+    const AdamRun run{{user_tab, item_tab, n_users, n_items, D}, m_u, v_u, m_i, v_i, last_u, last_i, lr, consts, n_consts, l2,
+                      beta1, beta2, eps, workspace, workspace_bytes, stream};
+    int32_t rc;
+    if ((rc = check_batch_range(plan, {first_batch, n_batches})) != WR_OK) return rc;
+    if ((rc = check_adam_steps(adam_step0, n_batches, n_consts)) != WR_OK) return rc;
+    for (int64_t k = 0; k < n_batches; ++k)
+        if ((rc = adam_catchup_and_step(run, batch_at(plan, first_batch + k), adam_step0 + k, at_or_null(loss_out, k))) != WR_OK)
+            return rc;
     return WR_OK;
 }
 
@@ -355,28 +364,12 @@ int32_t wr_bprmf_run_adam_lazy(float *user_tab, int64_t n_users, float *item_tab
 // average) the longest replay among a batch's rows is ~8x the mean, and a row's replay is one wave's serial chain — the
 // catch-up kernels then last as long as their unluckiest wave (steady state at 1M x 1M x 64, B = 2,048: 99 us per catch-up
 // launch, 196 at worst; the ~20 us figures of short runs only hold while no row has been idle for long).  Here every
-// step first sweeps ceil(rows / max_lag) consecutive rows of each table (a rotating window; wr_adam_catchup_all on the
-// sub-range) up to step t-1: after max_lag steps the whole table has been visited, so no row ever lags more than max_lag
-// steps, the batch rows' replays are short, and the bulk of the replay work — which exact dense-Adam semantics owe for every
-// row and step anyway — runs as uniform-length replays over thousands of waves.  A replay is a replay: the same
-// operations per row in the same order, so the tables stay bit-identical to the dense optimizer's.
+// step first sweeps ceil(rows / max_lag) consecutive rows of each table (a rotating window, walk_window;
+// wr_adam_catchup_all on the sub-range) up to step t-1: after max_lag steps the whole table has been visited, so no row ever
+// lags more than max_lag steps, the batch rows' replays are short, and the bulk of the replay work — which exact dense-Adam
+// semantics owe for every row and step anyway — runs as uniform-length replays over thousands of waves.  A replay is a
+// replay: the same operations per row in the same order, so the tables stay bit-identical to the dense optimizer's.
 // sweep_pos (host, in/out): [0] next user row of the window, [1] next item row.
-static int32_t sweep_window(float *tab, float *m, float *v, int32_t *last, int64_t n_rows, int32_t D, int64_t rows, int64_t *pos,
-                            int64_t upto, const float *consts, int64_t n_consts, float l2, float b1, float b2, float eps,
-                            void *stream) {
-    int64_t lo = *pos % n_rows, left = rows < n_rows ? rows : n_rows;
-    while (left > 0) {
-        const int64_t c = left < n_rows - lo ? left : n_rows - lo;
-        const int32_t rc = wr_adam_catchup_all(tab + lo * (int64_t)D, m + lo * (int64_t)D, v + lo * (int64_t)D, last + lo, c, D,
-                                               upto, consts, n_consts, l2, b1, b2, eps, stream);
-        if (rc != WR_OK) return rc;
-        lo = (lo + c) % n_rows;
-        left -= c;
-    }
-    *pos = lo;
-    return WR_OK;
-}
-
 int32_t wr_bprmf_run_adam_lazy_bounded(float *user_tab, int64_t n_users, float *item_tab, int64_t n_items, int32_t D,
                                        float *m_u, float *v_u, float *m_i, float *v_i, int32_t *last_u, int32_t *last_i,
                                        const int32_t *tu, const int32_t *tp, const int32_t *tn, const int32_t *oc_item,
@@ -385,29 +378,31 @@ int32_t wr_bprmf_run_adam_lazy_bounded(float *user_tab, int64_t n_users, float *
                                        float l2, float beta1, float beta2, float eps, float *loss_out, const wr_hot_runs *hot,
                                        int64_t max_lag, int64_t *sweep_pos, void *workspace, int64_t workspace_bytes,
                                        void *stream) {
-    WR_REQUIRE(n_triplets > 0 && batch_size > 0 && first_batch >= 0 && n_batches >= 0, WR_E_SHAPE, "bad batch range");
+    const PlanSpan plan{tu, tp, tn, oc_item, oc_src, n_triplets, batch_size, hot};
+    const BatchRange range{first_batch, n_batches};
+    int32_t rc;
+    WR_REQUIRE(batch_range_sane(plan, range), WR_E_SHAPE, "bad batch range");
     WR_REQUIRE(max_lag >= 1 && sweep_pos != nullptr, WR_E_RANGE, "max_lag must be >= 1 and sweep_pos given");
     WR_REQUIRE(n_users > 0 && n_items > 0 && sweep_pos[0] >= 0 && sweep_pos[1] >= 0, WR_E_SHAPE, "bad sweep position");
-    const int64_t total_batches = (n_triplets + batch_size - 1) / batch_size;
-    WR_REQUIRE(first_batch + n_batches <= total_batches, WR_E_SHAPE, "batches [%lld,%lld) exceed the plan's %lld",
-               (long long)first_batch, (long long)(first_batch + n_batches), (long long)total_batches);
-    WR_REQUIRE(adam_step0 >= 1 && adam_step0 + n_batches <= n_consts, WR_E_RANGE,
-               "adam steps [%lld,%lld) outside the consts table (%lld entries)", (long long)adam_step0,
-               (long long)(adam_step0 + n_batches), (long long)n_consts);
-    const int64_t rows_u = (n_users + max_lag - 1) / max_lag, rows_i = (n_items + max_lag - 1) / max_lag;
+    if ((rc = check_batch_range_fits(plan, range)) != WR_OK) return rc;
+    if ((rc = check_adam_steps(adam_step0, n_batches, n_consts)) != WR_OK) return rc;
+    float *tabs[2] = {user_tab, item_tab}, *m[2] = {m_u, m_i}, *v[2] = {v_u, v_i};
+    int32_t *lasts[2] = {last_u, last_i};
+    const int64_t n_rows[2] = {n_users, n_items};
     for (int64_t k = 0; k < n_batches; ++k) {
         const int64_t t = adam_step0 + k;
-        int32_t rc;
-        if (t > 1) {   // rows of the window -> step t-1 (zero-gradient steps; nothing to do before the first step)
-            if ((rc = sweep_window(user_tab, m_u, v_u, last_u, n_users, D, rows_u, &sweep_pos[0], t - 1, consts, n_consts, l2,
-                                   beta1, beta2, eps, stream)) != WR_OK) return rc;
-            if ((rc = sweep_window(item_tab, m_i, v_i, last_i, n_items, D, rows_i, &sweep_pos[1], t - 1, consts, n_consts, l2,
-                                   beta1, beta2, eps, stream)) != WR_OK) return rc;
+        // rows of the window -> step t-1 (zero-gradient steps; nothing to do before the first step)
+        for (int side = 0; side < 2 && t > 1; ++side) {
+            rc = walk_window(window_rows(n_rows[side], max_lag), n_rows[side], &sweep_pos[side], [&](int64_t lo, int64_t c) {
+                return wr_adam_catchup_all(tabs[side] + lo * (int64_t)D, m[side] + lo * (int64_t)D, v[side] + lo * (int64_t)D,
+                                           lasts[side] + lo, c, D, t - 1, consts, n_consts, l2, beta1, beta2, eps, stream);
+            });
+            if (rc != WR_OK) return rc;
         }
         if ((rc = wr_bprmf_run_adam_lazy(user_tab, n_users, item_tab, n_items, D, m_u, v_u, m_i, v_i, last_u, last_i, tu, tp, tn,
                                          oc_item, oc_src, n_triplets, batch_size, first_batch + k, 1, t, lr, consts, n_consts,
-                                         l2, beta1, beta2, eps, loss_out ? loss_out + k : nullptr, hot, workspace,
-                                         workspace_bytes, stream)) != WR_OK) return rc;
+                                         l2, beta1, beta2, eps, at_or_null(loss_out, k), hot, workspace, workspace_bytes,
+                                         stream)) != WR_OK) return rc;
     }
     return WR_OK;
 }
@@ -422,37 +417,23 @@ int32_t wr_bprmf_run_adam_folded(float *user_tab, int64_t n_users, float *item_t
                                  int64_t adam_step0, float lr, const float *consts, int64_t n_consts, float l2, float beta1,
                                  float beta2, float eps, float *loss_out, const wr_hot_runs *hot, void *workspace,
                                  int64_t workspace_bytes, void *stream) {
-    WR_REQUIRE(n_triplets > 0 && batch_size > 0 && first_batch >= 0 && n_batches >= 0, WR_E_SHAPE, "bad batch range");
-    const int64_t total_batches = (n_triplets + batch_size - 1) / batch_size;
-    WR_REQUIRE(first_batch + n_batches <= total_batches, WR_E_SHAPE, "batches [%lld,%lld) exceed the plan's %lld",
-               (long long)first_batch, (long long)(first_batch + n_batches), (long long)total_batches);
-    WR_REQUIRE(adam_step0 >= 1 && adam_step0 + n_batches <= n_consts, WR_E_RANGE,
-               "adam steps [%lld,%lld) outside the consts table (%lld entries)", (long long)adam_step0,
-               (long long)(adam_step0 + n_batches), (long long)n_consts);
+    const PlanSpan plan{tu, tp, tn, oc_item, oc_src, n_triplets, batch_size, hot};
+    const AdamRun run{{user_tab, item_tab, n_users, n_items, D}, m_u, v_u, m_i, v_i, last_u, last_i, lr, consts, n_consts, l2,
+                      beta1, beta2, eps, workspace, workspace_bytes, stream};
+    int32_t rc;
+    if ((rc = check_batch_range(plan, {first_batch, n_batches})) != WR_OK) return rc;
+    if ((rc = check_adam_steps(adam_step0, n_batches, n_consts)) != WR_OK) return rc;
     for (int64_t k = 0; k < n_batches; ++k) {
-        const int64_t b = first_batch + k, off = b * batch_size;
-        const int64_t Bk = (off + batch_size <= n_triplets) ? batch_size : (n_triplets - off);
+        const PlanBatch pb = batch_at(plan, first_batch + k);
         const int64_t t = adam_step0 + k;
-        int32_t rc;
-        const bool any_hot = hot != nullptr && hot->counts_host != nullptr &&
-                             (hot->counts_host[4 * b] | hot->counts_host[4 * b + 1] | hot->counts_host[4 * b + 2] |
-                              hot->counts_host[4 * b + 3]) != 0;
-        if (!any_hot) {
-            if ((rc = wr_bprmf_step_adam_folded(user_tab, n_users, item_tab, n_items, D, m_u, v_u, m_i, v_i, last_u, last_i,
-                                                tu + off, tp + off, tn + off, oc_item + 2 * off, oc_src + 2 * off, Bk, t, lr,
-                                                consts, n_consts, l2, beta1, beta2, eps, loss_out ? loss_out + k : nullptr,
-                                                workspace, workspace_bytes, stream)) != WR_OK) return rc;
-            continue;
-        }
-        wr_hot_runs hb = hot_at_batch(hot, b);
-        if ((rc = wr_adam_rows_lazy(user_tab, m_u, v_u, last_u, n_users, D, tu + off, Bk, nullptr, t, consts, n_consts, l2, beta1,
-                                    beta2, eps, stream)) != WR_OK) return rc;
-        if ((rc = wr_adam_rows_lazy(item_tab, m_i, v_i, last_i, n_items, D, oc_item + 2 * off, 2 * Bk, nullptr, t, consts,
-                                    n_consts, l2, beta1, beta2, eps, stream)) != WR_OK) return rc;
-        if ((rc = wr_bprmf_step_adam(user_tab, n_users, item_tab, n_items, D, m_u, v_u, m_i, v_i, last_u, last_i, tu + off,
-                                     tp + off, tn + off, oc_item + 2 * off, oc_src + 2 * off, Bk, t, lr, l2, beta1, beta2, eps,
-                                     loss_out ? loss_out + k : nullptr, &hb, workspace, workspace_bytes, stream)) != WR_OK)
-            return rc;
+        const int32_t *c = pb.has_hot ? pb.hot_runs.counts_host : nullptr;
+        if (c != nullptr && (c[0] | c[1] | c[2] | c[3]) != 0)
+            rc = adam_catchup_and_step(run, pb, t, at_or_null(loss_out, k));
+        else
+            rc = wr_bprmf_step_adam_folded(user_tab, n_users, item_tab, n_items, D, m_u, v_u, m_i, v_i, last_u, last_i, pb.tu,
+                                           pb.tp, pb.tn, pb.oc_item, pb.oc_src, pb.Bk, t, lr, consts, n_consts, l2, beta1, beta2,
+                                           eps, at_or_null(loss_out, k), workspace, workspace_bytes, stream);
+        if (rc != WR_OK) return rc;
     }
     return WR_OK;
 }
@@ -463,24 +444,17 @@ int32_t wr_bprmf_run_sgd_lazy(float *user_tab, int64_t n_users, float *item_tab,
                               int64_t n_triplets, int64_t batch_size, int64_t first_batch, int64_t n_batches, int64_t step0,
                               float lr, float l2, float *loss_out, const wr_hot_runs *hot, void *workspace,
                               int64_t workspace_bytes, void *stream) {
-    WR_REQUIRE(n_triplets > 0 && batch_size > 0 && first_batch >= 0 && n_batches >= 0 && step0 >= 1, WR_E_SHAPE,
-               "bad batch range");
-    const int64_t total_batches = (n_triplets + batch_size - 1) / batch_size;
-    WR_REQUIRE(first_batch + n_batches <= total_batches, WR_E_SHAPE, "batches [%lld,%lld) exceed the plan's %lld",
-               (long long)first_batch, (long long)(first_batch + n_batches), (long long)total_batches);
+    const PlanSpan plan{tu, tp, tn, oc_item, oc_src, n_triplets, batch_size, hot};
+    int32_t rc;
+    if ((rc = check_batch_range(plan, {first_batch, n_batches}, step0 >= 1)) != WR_OK) return rc;
     for (int64_t k = 0; k < n_batches; ++k) {
-        const int64_t b = first_batch + k, off = b * batch_size;
-        const int64_t Bk = (off + batch_size <= n_triplets) ? batch_size : (n_triplets - off);
-        int32_t rc;
-        wr_hot_runs hb;
-        if (hot != nullptr) hb = hot_at_batch(hot, b);
-        if ((rc = wr_sgd_rows_lazy(user_tab, last_u, n_users, D, tu + off, Bk, step0 + k, lr, l2, stream)) != WR_OK) return rc;
-        if ((rc = wr_sgd_rows_lazy(item_tab, last_i, n_items, D, oc_item + 2 * off, 2 * Bk, step0 + k, lr, l2, stream)) != WR_OK)
+        const PlanBatch pb = batch_at(plan, first_batch + k);
+        if ((rc = wr_sgd_rows_lazy(user_tab, last_u, n_users, D, pb.tu, pb.Bk, step0 + k, lr, l2, stream)) != WR_OK) return rc;
+        if ((rc = wr_sgd_rows_lazy(item_tab, last_i, n_items, D, pb.oc_item, 2 * pb.Bk, step0 + k, lr, l2, stream)) != WR_OK)
             return rc;
-        if ((rc = wr_bprmf_step_sgd(user_tab, n_users, item_tab, n_items, D, tu + off, tp + off, tn + off, oc_item + 2 * off,
-                                    oc_src + 2 * off, Bk, lr, l2, stamp_u, stamp_i, step_id0 + (int32_t)k,
-                                    loss_out ? loss_out + k : nullptr, hot ? &hb : nullptr, workspace, workspace_bytes,
-                                    stream)) != WR_OK) return rc;
+        if ((rc = wr_bprmf_step_sgd(user_tab, n_users, item_tab, n_items, D, pb.tu, pb.tp, pb.tn, pb.oc_item, pb.oc_src, pb.Bk, lr,
+                                    l2, stamp_u, stamp_i, step_id0 + (int32_t)k, at_or_null(loss_out, k), pb.hot(), workspace,
+                                    workspace_bytes, stream)) != WR_OK) return rc;
     }
     return WR_OK;
 }
@@ -498,7 +472,6 @@ int32_t wr_bprmf_run_sgd_lazy_bounded(float *user_tab, int64_t n_users, float *i
     WR_REQUIRE(max_lag >= 1 && sweep_pos != nullptr && sweep_pos[0] >= 0 && sweep_pos[1] >= 0, WR_E_RANGE,
                "max_lag must be >= 1 and sweep_pos given");
     WR_REQUIRE(n_users > 0 && n_items > 0 && n_batches >= 0 && step0 >= 1, WR_E_SHAPE, "bad sizes");
-    const int64_t rows[2] = {(n_users + max_lag - 1) / max_lag, (n_items + max_lag - 1) / max_lag};
     float *tabs[2] = {user_tab, item_tab};
     int32_t *lasts[2] = {last_u, last_i};
     const int64_t n_rows[2] = {n_users, n_items};
@@ -506,20 +479,15 @@ int32_t wr_bprmf_run_sgd_lazy_bounded(float *user_tab, int64_t n_users, float *i
         int32_t rc;
         const int64_t t = step0 + k;
         for (int side = 0; side < 2 && t > 1; ++side) {
-            int64_t lo = sweep_pos[side] % n_rows[side], left = rows[side] < n_rows[side] ? rows[side] : n_rows[side];
-            while (left > 0) {
-                const int64_t c = left < n_rows[side] - lo ? left : n_rows[side] - lo;
-                if ((rc = wr_sgd_catchup_all(tabs[side] + lo * (int64_t)D, lasts[side] + lo, c, D, t - 1, lr, l2, stream)) != WR_OK)
-                    return rc;
-                lo = (lo + c) % n_rows[side];
-                left -= c;
-            }
-            sweep_pos[side] = lo;
+            rc = walk_window(window_rows(n_rows[side], max_lag), n_rows[side], &sweep_pos[side], [&](int64_t lo, int64_t c) {
+                return wr_sgd_catchup_all(tabs[side] + lo * (int64_t)D, lasts[side] + lo, c, D, t - 1, lr, l2, stream);
+            });
+            if (rc != WR_OK) return rc;
         }
         if ((rc = wr_bprmf_run_sgd_lazy(user_tab, n_users, item_tab, n_items, D, last_u, last_i, stamp_u, stamp_i,
                                         step_id0 + (int32_t)k, tu, tp, tn, oc_item, oc_src, n_triplets, batch_size,
-                                        first_batch + k, 1, t, lr, l2, loss_out ? loss_out + k : nullptr, hot, workspace,
-                                        workspace_bytes, stream)) != WR_OK) return rc;
+                                        first_batch + k, 1, t, lr, l2, at_or_null(loss_out, k), hot, workspace, workspace_bytes,
+                                        stream)) != WR_OK) return rc;
     }
     return WR_OK;
 }
@@ -527,8 +495,7 @@ int32_t wr_bprmf_run_sgd_lazy_bounded(float *user_tab, int64_t n_users, float *i
 int32_t wr_adadelta_decay_all(float *square_avg, float *acc_delta, int32_t *last_step, int64_t n_rows, int32_t D, int64_t step,
                               float rho, void *stream_) {
     int32_t rc;
-    if ((rc = check_table(square_avg, n_rows, D, "square_avg")) != WR_OK) return rc;
-    if ((rc = check_table(acc_delta, n_rows, D, "acc_delta")) != WR_OK) return rc;
+    if ((rc = check_tables({{square_avg, n_rows, "square_avg"}, {acc_delta, n_rows, "acc_delta"}}, D)) != WR_OK) return rc;
     WR_REQUIRE(last_step != nullptr, WR_E_NULL, "last_step is NULL");
     WR_REQUIRE(step >= 0 && step < INT32_MAX, WR_E_RANGE, "step must be >= 0");
     const int64_t g = (n_rows + kBlock / kWave - 1) / (kBlock / kWave), cap = 256 * 64;

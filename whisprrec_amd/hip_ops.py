@@ -19,6 +19,38 @@ def _p(t):
     return None if t is None else t.data_ptr()
 
 
+def _addr(struct):
+    """address of a ctypes struct / array, or None"""
+    return ctypes.addressof(struct) if struct is not None else None
+
+
+def _event_handles(events, per_step, count, allow_none):
+    """the hipEvent_t handles of `per_step * count` ``torch.cuda.Event(enable_timing=True)`` as a c_void_p array for the
+    step entries' timing hooks (None: no hooks).  allow_none: single entries may be None."""
+    if events is None:
+        return None
+    if len(events) != per_step * count:
+        raise ValueError("%s must hold %d events per step" % ("phase_events" if per_step == 4 else "events", per_step))
+    handles = []
+    for e in events:
+        if e is None and allow_none:
+            handles.append(None)
+            continue
+        if not e.cuda_event:  # torch creates the hipEvent_t lazily on first record
+            e.record()
+        handles.append(e.cuda_event)
+    return (ctypes.c_void_p * len(handles))(*handles)
+
+
+def _auto_lag(state, plan):
+    """max_lag of an optimizer state: its own setting, or (None) MAX_LAG when a row misses more than LAG_MIN_GAP steps between
+    two uses on average (rows / batch), else 0 = unbounded"""
+    if state.max_lag is None:
+        gap = max(state.tabs.U.shape[0], state.tabs.I.shape[0]) / float(max(plan.batch_size, 1))
+        return state.MAX_LAG if gap > state.LAG_MIN_GAP else 0
+    return state.max_lag
+
+
 def _req(t, dtype, name, ndim=None):
     if not isinstance(t, torch.Tensor):
         raise TypeError("%s must be a torch.Tensor" % name)
@@ -739,7 +771,21 @@ class BprmfTables:
         nbytes = abi.check_size(abi.lib().wr_bprmf_step_workspace_bytes(B, self.D), "wr_bprmf_step_workspace_bytes")
         return workspace(self.dev, "step").get(nbytes)
 
+    def _loss_buf(self, out, count=None):
+        """the caller's loss tensor, or a new one: a scalar, or one float per step"""
+        return out if out is not None else torch.empty(() if count is None else count, dtype=torch.float32, device=self.dev)
+
+    def _table_head(self):
+        """(U, n_users, I, n_items, D): how every step entry's argument list starts"""
+        return (_p(self.U), self.U.shape[0], _p(self.I), self.I.shape[0], self.D)
+
+    @staticmethod
+    def _plan_head(plan):
+        """(tu, tp, tn, oc_item, oc_src, n_triplets, batch_size): the sorted plan in the run entries' argument lists"""
+        return (_p(plan.tu), _p(plan.tp), _p(plan.tn), _p(plan.oc_item), _p(plan.oc_src), plan.n_triplets, plan.batch_size)
+
     def _plan_ptrs(self, plan, k):
+        """(tu, tp, tn, oc_item, oc_src, B) of batch k: the plan in the single-step entries' argument lists"""
         off = k * plan.batch_size
         return (plan.tu.data_ptr() + 4 * off, plan.tp.data_ptr() + 4 * off, plan.tn.data_ptr() + 4 * off,
                 plan.oc_item.data_ptr() + 8 * off, plan.oc_src.data_ptr() + 8 * off, plan.batch_len(k))
@@ -748,19 +794,15 @@ class BprmfTables:
         """One BaseRunner.fit iteration (zero_grad/predict/backward/SGD.step, BaseRunner.py:196-199) on batch k.
         decay_untouched=False leaves the weight decay of the rows outside the batch to LazyOptimizerState."""
         L = abi.lib()
-        tu, tp, tn, oi, os_, B = self._plan_ptrs(plan, k)
         ws = self._ws(plan.batch_size)
-        if loss_out is None:
-            loss_out = torch.empty((), dtype=torch.float32, device=self.dev)
+        loss_out = self._loss_buf(loss_out)
         su = si = None
         self.step_id += 1
         if l2 != 0.0:
             su, si = self._stamps()
         hot = plan.hot_struct(k)
-        abi.check(L.wr_bprmf_step_sgd(_p(self.U), self.U.shape[0], _p(self.I), self.I.shape[0], self.D, tu, tp, tn, oi,
-                                      os_, B, lr, l2, _p(su), _p(si), self.step_id, _p(loss_out),
-                                      ctypes.addressof(hot) if hot is not None else None, _p(ws), ws.numel(),
-                                      _stream()), "wr_bprmf_step_sgd")
+        abi.check(L.wr_bprmf_step_sgd(*self._table_head(), *self._plan_ptrs(plan, k), lr, l2, _p(su), _p(si), self.step_id,
+                                      _p(loss_out), _addr(hot), _p(ws), ws.numel(), _stream()), "wr_bprmf_step_sgd")
         if l2 != 0.0 and decay_untouched:  # dense weight decay on the rows the batch did not touch (torch.optim.SGD semantics)
             abi.check(L.wr_sgd_decay_untouched(_p(self.U), self.U.shape[0], self.D, _p(su), self.step_id, lr, l2,
                                                _stream()), "wr_sgd_decay_untouched")
@@ -775,28 +817,11 @@ class BprmfTables:
         start / stop events of its two phases (include/whisprrec_hip.h; bench.py's per-kernel timing)."""
         L = abi.lib()
         ws = self._ws(plan.batch_size)
-        if losses is None:
-            losses = torch.empty(count, dtype=torch.float32, device=self.dev)
+        losses = self._loss_buf(losses, count)
         hot = plan.hot_struct()
-        ev = None
-        if phase_events is not None:
-            if len(phase_events) != 4 * count:
-                raise ValueError("phase_events must hold 4 events per step")
-            handles = []
-            for e in phase_events:
-                if e is None:
-                    handles.append(None)
-                    continue
-                if not e.cuda_event:  # torch creates the hipEvent_t lazily on first record
-                    e.record()
-                handles.append(e.cuda_event)
-            ev = (ctypes.c_void_p * len(handles))(*handles)
-        abi.check(L.wr_bprmf_run_sgd(_p(self.U), self.U.shape[0], _p(self.I), self.I.shape[0], self.D, _p(plan.tu),
-                                     _p(plan.tp), _p(plan.tn), _p(plan.oc_item), _p(plan.oc_src), plan.n_triplets,
-                                     plan.batch_size, first, count, lr, _p(losses),
-                                     ctypes.addressof(ev) if ev is not None else None,
-                                     ctypes.addressof(hot) if hot is not None else None, _p(ws), ws.numel(), _stream()),
-                  "wr_bprmf_run_sgd")
+        ev = _event_handles(phase_events, 4, count, True)
+        abi.check(L.wr_bprmf_run_sgd(*self._table_head(), *self._plan_head(plan), first, count, lr, _p(losses), _addr(ev),
+                                     _addr(hot), _p(ws), ws.numel(), _stream()), "wr_bprmf_run_sgd")
         self.step_id += count
         return losses
 
@@ -852,29 +877,13 @@ class BprmfTables:
         o = plan.overlap
         if ws is None:
             ws = self.overlap_workspace(plan.batch_size)
-        if losses is None:
-            losses = torch.empty(count, dtype=torch.float32, device=self.dev)
-        ev = None
-        if phase_events is not None:
-            if len(phase_events) != 4 * count:
-                raise ValueError("phase_events must hold 4 events per step")
-            handles = []
-            for e in phase_events:
-                if e is None:
-                    handles.append(None)
-                    continue
-                if not e.cuda_event:
-                    e.record()
-                handles.append(e.cuda_event)
-            ev = (ctypes.c_void_p * len(handles))(*handles)
+        losses = self._loss_buf(losses, count)
+        ev = _event_handles(phase_events, 4, count, True)
         sync = self._chain_sync(count)
-        abi.check(L.wr_bprmf_run_sgd_chain(_p(self.U), self.U.shape[0], _p(self.I), self.I.shape[0], self.D, _p(plan.tu),
-                                           _p(plan.tp), _p(plan.tn), _p(plan.oc_item), _p(plan.oc_src), plan.n_triplets,
-                                           plan.batch_size, first, count, lr, _p(losses), _p(o["tdef"]), _p(o["def_q"]),
-                                           o["def_count_host"].data_ptr(), o["cap"],
-                                           o["cap"] if def_limit is None else int(def_limit),
-                                           ctypes.addressof(ev) if ev is not None else None, _p(ws), ws.numel(), _p(sync),
-                                           sync.numel(), _stream()), "wr_bprmf_run_sgd_chain")
+        abi.check(L.wr_bprmf_run_sgd_chain(*self._table_head(), *self._plan_head(plan), first, count, lr, _p(losses),
+                                           _p(o["tdef"]), _p(o["def_q"]), o["def_count_host"].data_ptr(), o["cap"],
+                                           o["cap"] if def_limit is None else int(def_limit), _addr(ev), _p(ws), ws.numel(),
+                                           _p(sync), sync.numel(), _stream()), "wr_bprmf_run_sgd_chain")
         self.step_id += count
         return losses
 
@@ -899,24 +908,13 @@ class BprmfTables:
         L = abi.lib()
         nbytes = abi.check_size(L.wr_bprmf_group_workspace_bytes(gplan.batch_size, self.D), "wr_bprmf_group_workspace_bytes")
         ws = workspace(self.dev, "group_step").get(nbytes)
-        if losses is None:
-            losses = torch.empty(count, dtype=torch.float32, device=self.dev)
-        ev = None
-        if events is not None:
-            if len(events) != 2 * count:
-                raise ValueError("events must hold 2 events per step")
-            handles = []
-            for e in events:
-                if not e.cuda_event:
-                    e.record()
-                handles.append(e.cuda_event)
-            ev = (ctypes.c_void_p * len(handles))(*handles)
+        losses = self._loss_buf(losses, count)
+        ev = _event_handles(events, 2, count, False)
         sync = self._group_sync(count)
-        abi.check(L.wr_bprmf_run_sgd_group(_p(self.U), self.U.shape[0], _p(self.I), self.I.shape[0], self.D, _p(gplan.u),
-                                           _p(gplan.p), _p(gplan.n), gplan.n_triplets, gplan.batch_size, _p(gplan.buf),
-                                           gplan.buf.numel(), first, count, lr, _p(losses),
-                                           ctypes.addressof(ev) if ev is not None else None, _p(ws), ws.numel(), _p(sync),
-                                           sync.numel(), _stream()), "wr_bprmf_run_sgd_group")
+        abi.check(L.wr_bprmf_run_sgd_group(*self._table_head(), _p(gplan.u), _p(gplan.p), _p(gplan.n), gplan.n_triplets,
+                                           gplan.batch_size, _p(gplan.buf), gplan.buf.numel(), first, count, lr, _p(losses),
+                                           _addr(ev), _p(ws), ws.numel(), _p(sync), sync.numel(), _stream()),
+                  "wr_bprmf_run_sgd_group")
         self.step_id += count
         return losses
 
@@ -925,17 +923,13 @@ class BprmfTables:
         batch into grad_u / grad_i and stamps them with the returned step id (other rows are not written).
         stamps=False: no stamp arrays at all — for a caller that zero-filled grad_u / grad_i and reads them densely."""
         L = abi.lib()
-        tu, tp, tn, oi, os_, B = self._plan_ptrs(plan, k)
         ws = self._ws(plan.batch_size)
         su, si = self._stamps() if stamps else (None, None)
-        if loss_out is None:
-            loss_out = torch.empty((), dtype=torch.float32, device=self.dev)
+        loss_out = self._loss_buf(loss_out)
         self.step_id += 1
         hot = plan.hot_struct(k)
-        abi.check(L.wr_bprmf_grads(_p(self.U), self.U.shape[0], _p(self.I), self.I.shape[0], self.D, tu, tp, tn, oi, os_,
-                                   B, _p(grad_u), _p(grad_i), _p(su), _p(si), self.step_id, _p(loss_out),
-                                   ctypes.addressof(hot) if hot is not None else None, _p(ws), ws.numel(), _stream()),
-                  "wr_bprmf_grads")
+        abi.check(L.wr_bprmf_grads(*self._table_head(), *self._plan_ptrs(plan, k), _p(grad_u), _p(grad_i), _p(su), _p(si),
+                                   self.step_id, _p(loss_out), _addr(hot), _p(ws), ws.numel(), _stream()), "wr_bprmf_grads")
         return loss_out, self.step_id
 
 
@@ -1649,11 +1643,8 @@ class LazyOptimizerState:
             return gap <= self.FOLD_MAX_GAP
         return self.fold
 
-    def _lag(self, plan):
-        if self.max_lag is None:
-            gap = max(self.tabs.U.shape[0], self.tabs.I.shape[0]) / float(max(plan.batch_size, 1))
-            return self.MAX_LAG if gap > self.LAG_MIN_GAP else 0
-        return self.max_lag
+    def _adam_state(self):
+        return (_p(self.m_u), _p(self.v_u), _p(self.m_i), _p(self.v_i), _p(self.last_u), _p(self.last_i))
 
     def _grow_consts(self, n):
         host = torch.empty(2 * n, dtype=torch.float32)
@@ -1669,39 +1660,31 @@ class LazyOptimizerState:
     def step(self, plan, k, loss_out=None):
         """optimizer step on batch k of the plan (gradient computation included); returns the loss tensor"""
         tabs = self.tabs
-        if self._lag(plan) > 0 and not (self.name == "Adam" and self._folds(plan)):
+        if _auto_lag(self, plan) > 0 and not (self.name == "Adam" and self._folds(plan)):
             out = self.run(plan, k, 1, losses=None if loss_out is None else loss_out.reshape(1))   # keeps the window turning
             return out.reshape(()) if loss_out is None else loss_out
         self.t += 1
-        tu, _, _, oi, _, B = tabs._plan_ptrs(plan, k)
+        batch = tabs._plan_ptrs(plan, k)
+        tu, oi, B = batch[0], batch[3], batch[5]
         if self.name == "Adam":
             if self.t >= self.n_consts:
                 self._grow_consts(2 * self.n_consts)
-            if self._folds(plan) and plan.hot_struct(k) is None:
-                if loss_out is None:
-                    loss_out = torch.empty((), dtype=torch.float32, device=tabs.dev)
-                _, tp, tn, _, os_, _ = tabs._plan_ptrs(plan, k)
-                ws = tabs._ws(plan.batch_size)
-                abi.check(abi.lib().wr_bprmf_step_adam_folded(
-                    _p(tabs.U), tabs.U.shape[0], _p(tabs.I), tabs.I.shape[0], tabs.D, _p(self.m_u), _p(self.v_u), _p(self.m_i),
-                    _p(self.v_i), _p(self.last_u), _p(self.last_i), tu, tp, tn, oi, os_, B, self.t, self.lr, _p(self.consts),
-                    self.n_consts, self.l2, self.betas[0], self.betas[1], self.eps, _p(loss_out), _p(ws), ws.numel(), _stream()),
-                    "wr_bprmf_step_adam_folded")
-                tabs.step_id += 1
-                return loss_out
-            self._adam_rows(tabs.U, self.m_u, self.v_u, self.last_u, tu, B, None)       # the batch's rows up to t-1
-            self._adam_rows(tabs.I, self.m_i, self.v_i, self.last_i, oi, 2 * B, None)
-            # gradients + Adam on the rows the step kernels finish (no gradient table)
-            if loss_out is None:
-                loss_out = torch.empty((), dtype=torch.float32, device=tabs.dev)
-            _, tp, tn, _, os_, _ = tabs._plan_ptrs(plan, k)
-            ws = tabs._ws(plan.batch_size)
             hot = plan.hot_struct(k)
-            abi.check(abi.lib().wr_bprmf_step_adam(
-                _p(tabs.U), tabs.U.shape[0], _p(tabs.I), tabs.I.shape[0], tabs.D, _p(self.m_u), _p(self.v_u), _p(self.m_i),
-                _p(self.v_i), _p(self.last_u), _p(self.last_i), tu, tp, tn, oi, os_, B, self.t, self.lr, self.l2,
-                self.betas[0], self.betas[1], self.eps, _p(loss_out), ctypes.addressof(hot) if hot is not None else None,
-                _p(ws), ws.numel(), _stream()), "wr_bprmf_step_adam")
+            folded = self._folds(plan) and hot is None
+            if not folded:
+                self._adam_rows(tabs.U, self.m_u, self.v_u, self.last_u, tu, B, None)       # the batch's rows up to t-1
+                self._adam_rows(tabs.I, self.m_i, self.v_i, self.last_i, oi, 2 * B, None)
+            # gradients + Adam on the rows the step kernels finish (no gradient table); folded: the catch-up rides in their loads
+            loss_out = tabs._loss_buf(loss_out)
+            ws = tabs._ws(plan.batch_size)
+            head = (*tabs._table_head(), *self._adam_state(), *batch, self.t, self.lr)
+            tail = (self.l2, self.betas[0], self.betas[1], self.eps, _p(loss_out))
+            if folded:
+                abi.check(abi.lib().wr_bprmf_step_adam_folded(*head, _p(self.consts), self.n_consts, *tail, _p(ws), ws.numel(),
+                                                              _stream()), "wr_bprmf_step_adam_folded")
+            else:
+                abi.check(abi.lib().wr_bprmf_step_adam(*head, *tail, _addr(hot), _p(ws), ws.numel(), _stream()),
+                          "wr_bprmf_step_adam")
             tabs.step_id += 1
             return loss_out
         L = abi.lib()
@@ -1714,22 +1697,17 @@ class LazyOptimizerState:
         """`count` consecutive optimizer steps on batches [first, first + count) of the plan, issued from native code
         (wr_bprmf_run_adam_lazy / wr_bprmf_run_sgd_lazy); same result as `count` calls of step()"""
         tabs, L = self.tabs, abi.lib()
-        if losses is None:
-            losses = torch.empty(count, dtype=torch.float32, device=tabs.dev)
+        losses = tabs._loss_buf(losses, count)
         ws = tabs._ws(plan.batch_size)
         su, si = tabs._stamps()
         hot = plan.hot_struct()
-        hp = ctypes.addressof(hot) if hot is not None else None
         t0 = self.t + 1
+        lag = _auto_lag(self, plan)
         if self.name == "Adam":
             while self.t + count >= self.n_consts:
                 self._grow_consts(2 * self.n_consts)
-            head = (_p(tabs.U), tabs.U.shape[0], _p(tabs.I), tabs.I.shape[0], tabs.D, _p(self.m_u), _p(self.v_u), _p(self.m_i),
-                    _p(self.v_i), _p(self.last_u), _p(self.last_i),
-                    _p(plan.tu), _p(plan.tp), _p(plan.tn), _p(plan.oc_item), _p(plan.oc_src), plan.n_triplets, plan.batch_size,
-                    first, count, t0, self.lr, _p(self.consts), self.n_consts, self.l2, self.betas[0], self.betas[1], self.eps,
-                    _p(losses), hp)
-            lag = self._lag(plan)
+            head = (*tabs._table_head(), *self._adam_state(), *tabs._plan_head(plan), first, count, t0, self.lr,
+                    _p(self.consts), self.n_consts, self.l2, self.betas[0], self.betas[1], self.eps, _p(losses), _addr(hot))
             o = getattr(plan, "overlap", None)
             if self._folds(plan) and self.chain and o is not None and hot is None and count >= 2 and tabs.chain_supported():
                 # one launch per step: the item phase of step k-1 inside the launch of step k's user phase
@@ -1743,18 +1721,16 @@ class LazyOptimizerState:
             elif self._folds(plan):
                 abi.check(L.wr_bprmf_run_adam_folded(*head, _p(ws), ws.numel(), _stream()), "wr_bprmf_run_adam_folded")
             elif lag > 0:
-                abi.check(L.wr_bprmf_run_adam_lazy_bounded(*head, lag, ctypes.addressof(self._sweep_pos), _p(ws), ws.numel(),
-                                                           _stream()), "wr_bprmf_run_adam_lazy_bounded")
+                abi.check(L.wr_bprmf_run_adam_lazy_bounded(*head, lag, _addr(self._sweep_pos), _p(ws), ws.numel(), _stream()),
+                          "wr_bprmf_run_adam_lazy_bounded")
             else:
                 abi.check(L.wr_bprmf_run_adam_lazy(*head, _p(ws), ws.numel(), _stream()), "wr_bprmf_run_adam_lazy")
         else:
-            head = (_p(tabs.U), tabs.U.shape[0], _p(tabs.I), tabs.I.shape[0], tabs.D, _p(self.last_u), _p(self.last_i), _p(su),
-                    _p(si), tabs.step_id + 1, _p(plan.tu), _p(plan.tp), _p(plan.tn), _p(plan.oc_item), _p(plan.oc_src),
-                    plan.n_triplets, plan.batch_size, first, count, t0, self.lr, self.l2, _p(losses), hp)
-            lag = self._lag(plan)
+            head = (*tabs._table_head(), _p(self.last_u), _p(self.last_i), _p(su), _p(si), tabs.step_id + 1,
+                    *tabs._plan_head(plan), first, count, t0, self.lr, self.l2, _p(losses), _addr(hot))
             if lag > 0:
-                abi.check(L.wr_bprmf_run_sgd_lazy_bounded(*head, lag, ctypes.addressof(self._sweep_pos), _p(ws), ws.numel(),
-                                                          _stream()), "wr_bprmf_run_sgd_lazy_bounded")
+                abi.check(L.wr_bprmf_run_sgd_lazy_bounded(*head, lag, _addr(self._sweep_pos), _p(ws), ws.numel(), _stream()),
+                          "wr_bprmf_run_sgd_lazy_bounded")
             else:
                 abi.check(L.wr_bprmf_run_sgd_lazy(*head, _p(ws), ws.numel(), _stream()), "wr_bprmf_run_sgd_lazy")
         self.t += count
@@ -1768,13 +1744,13 @@ class LazyOptimizerState:
         L, tabs = abi.lib(), self.tabs
         if self.name == "Adam":
             for tab, m, v, last in ((tabs.U, self.m_u, self.v_u, self.last_u), (tabs.I, self.m_i, self.v_i, self.last_i)):
-                abi.check(L.wr_adam_catchup_all(_p(tab), _p(m), _p(v), _p(last), tab.shape[0], tab.shape[1], self.t,
-                                                _p(self.consts), self.n_consts, self.l2, self.betas[0], self.betas[1],
-                                                self.eps, _stream()), "wr_adam_catchup_all")
+                abi.check(L.wr_adam_catchup_all(_p(tab), _p(m), _p(v), _p(last), *tab.shape, self.t, _p(self.consts),
+                                                self.n_consts, self.l2, self.betas[0], self.betas[1], self.eps, _stream()),
+                          "wr_adam_catchup_all")
         else:
             for tab, last in ((tabs.U, self.last_u), (tabs.I, self.last_i)):
-                abi.check(L.wr_sgd_catchup_all(_p(tab), _p(last), tab.shape[0], tab.shape[1], self.t, self.lr, self.l2,
-                                               _stream()), "wr_sgd_catchup_all")
+                abi.check(L.wr_sgd_catchup_all(_p(tab), _p(last), *tab.shape, self.t, self.lr, self.l2, _stream()),
+                          "wr_sgd_catchup_all")
         self.flushed_at = self.t
 
 
@@ -1808,21 +1784,16 @@ class StatefulSparseState:
 
     def run(self, plan, first, count, losses=None):
         tabs = self.tabs
-        if losses is None:
-            losses = torch.empty(count, dtype=torch.float32, device=tabs.dev)
+        losses = tabs._loss_buf(losses, count)
         ws = tabs._ws(plan.batch_size)
         hot = plan.hot_struct()
-        head = (self.KIND[self.name], _p(tabs.U), tabs.U.shape[0], _p(tabs.I), tabs.I.shape[0], tabs.D, _p(self.s1_u),
-                _p(self.s2_u), _p(self.s1_i), _p(self.s2_i), _p(self.last_u), _p(self.last_i), _p(plan.tu), _p(plan.tp), _p(plan.tn),
-                _p(plan.oc_item), _p(plan.oc_src), plan.n_triplets, plan.batch_size, first, count, self.t + 1, self.lr, self.rho,
-                self.eps, _p(losses), ctypes.addressof(hot) if hot is not None else None)
-        lag = self.max_lag
-        if lag is None:
-            gap = max(tabs.U.shape[0], tabs.I.shape[0]) / float(max(plan.batch_size, 1))
-            lag = self.MAX_LAG if gap > self.LAG_MIN_GAP else 0
+        head = (self.KIND[self.name], *tabs._table_head(), _p(self.s1_u), _p(self.s2_u), _p(self.s1_i), _p(self.s2_i),
+                _p(self.last_u), _p(self.last_i), *tabs._plan_head(plan), first, count, self.t + 1, self.lr, self.rho, self.eps,
+                _p(losses), _addr(hot))
+        lag = _auto_lag(self, plan)
         if self.name == "Adadelta" and lag > 0:
-            abi.check(abi.lib().wr_bprmf_run_stateful_bounded(*head, lag, ctypes.addressof(self._sweep_pos), _p(ws), ws.numel(),
-                                                              _stream()), "wr_bprmf_run_stateful_bounded")
+            abi.check(abi.lib().wr_bprmf_run_stateful_bounded(*head, lag, _addr(self._sweep_pos), _p(ws), ws.numel(), _stream()),
+                      "wr_bprmf_run_stateful_bounded")
         else:
             abi.check(abi.lib().wr_bprmf_run_stateful(*head, _p(ws), ws.numel(), _stream()), "wr_bprmf_run_stateful")
         self.t += count
