@@ -15,6 +15,7 @@ Reference entry points exercised (paths relative to /root/reference):
       (BaseRunner.py:180-201) on ml-100k, seed 3407
   G3  src/models/BaseModel.py:167-177 (negative sampler, NumPy MT19937 stream)
   G4  src/models/general/LightGCN.py:54-175 (adjacency, forward, predict, grads)
+  G11 the same entry points as G4 on G4's own inputs, at a reg_weight where the EmbLoss term is 0.3 .. 0.8 of the gradient
   G5  src/models/sequential/SASRec.py:84,105-106 (item-embedding gather / scatter with padding_idx=0)
   G6  src/helpers/BaseRunner.py:50-92 (evaluate_method)
   G8  src/helpers/BaseReader.py + src/utils/sample.py on data/ml-100k/ml-100k.inter: filtered ids, both split rules
@@ -382,6 +383,35 @@ def g4_lightgcn():
     save("g4_lightgcn", **out)
 
 
+# --------------------------------------------------------------------------------------------- G11
+def g11_lightgcn_reg():
+    """LightGCN.predict + backward on g4's graph, tables and batch (read from g4_lightgcn.npz, not stored again) at ONE
+    reg_weight at which the EmbLoss term is about half of the gradient: at g4's 1e-5 it is 2e-6 of it, below every bound."""
+    sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
+    from oracle import lightgcn_parity as lp
+    g4 = np.load(os.path.join(HERE, "g4_lightgcn.npz"))
+    nU, nI, D, L = g4["U0"].shape[0], g4["I0"].shape[0], g4["U0"].shape[1], int(g4["hp"][0])
+    ptr, idx = g4["clicked_ptr"], g4["clicked_idx"]
+    clicked = {u: set(int(x) for x in idx[ptr[u]:ptr[u + 1]]) for u in range(nU) if ptr[u + 1] > ptr[u]}
+    _, _, g_bpr, g1 = lp.g4_terms_f64(g4, 1.0)
+    rw = lp.reg_weight_for_share(g_bpr, g1)
+    _, _, g_bpr, g_reg = lp.g4_terms_f64(g4, rw)
+    share = lp.reg_share(g_bpr, g_reg)
+    assert lp.SHARE[0] <= share <= lp.SHARE[1], share
+    torch.manual_seed(3407)
+    model = LightGCN(_args(embedding_size=D, gcn_layers=L, reg_weight=rw), _Corpus(nU, nI, clicked))
+    with torch.no_grad():
+        model.user_embedding.weight.copy_(torch.from_numpy(g4["U0"]))
+        model.item_embedding.weight.copy_(torch.from_numpy(g4["I0"]))
+    fd = {"user_id": torch.from_numpy(g4["u"]), "pos_item": torch.from_numpy(g4["p"]), "neg_items": torch.from_numpy(g4["n"])}
+    loss = model.predict(fd)
+    loss.backward()
+    print("g11: reg_weight %g, share of the gradient %.3f, loss %.6f" % (rw, share, float(loss.detach())))
+    save("g11_lightgcn_reg", reg_weight=np.asarray([rw], dtype=np.float64),
+         loss=loss.detach().numpy().reshape(1).astype(np.float32),
+         gU=model.user_embedding.weight.grad.numpy().copy(), gI=model.item_embedding.weight.grad.numpy().copy())
+
+
 # --------------------------------------------------------------------------------------------- G5
 def g5_sasrec_emb():
     torch.manual_seed(3407)
@@ -577,4 +607,4 @@ if __name__ == "__main__":
     for w in which:
         {"g1": g1_bprmf_step, "g2": g2_ml100k_curve, "g3": g3_sampler, "g4": g4_lightgcn,
          "g5": g5_sasrec_emb, "g6": g6_eval, "g7": g7_sgl, "g8": g8_reader, "g9": g9_end_to_end,
-         "inter": ml100k_inter}[w]()
+         "g11": g11_lightgcn_reg, "inter": ml100k_inter}[w]()

@@ -6,10 +6,17 @@ import numpy as np
 import pytest
 import torch
 
+import oracle
 from conftest import rel_err
+from oracle import lightgcn_parity as lp
 from whisprrec_amd import host
 
 TOL = 1e-5
+
+
+@pytest.fixture(scope="module")
+def g11():
+    return oracle.load_golden("g11_lightgcn_reg")
 
 
 def _corpus(g4):
@@ -297,6 +304,66 @@ def test_native_step_equals_the_call_by_call_step(g4):
     m = _model(g4, dev)
     with pytest.raises(IndexError):
         m.predict(bad)
+
+
+@pytest.mark.gpu
+def test_loss_and_grads_match_reference_where_the_reg_term_counts(g4, g11):
+    """g4's inputs at g11's reg_weight: EmbLoss is about half of the gradient there (2e-6 of it at g4's own 1e-5, where
+    embloss_grad_kernel could add nothing and every assertion above would hold).  One native call and the call-by-call form:
+    the same bits, and each within TOL of the reference and, per row, within the derived TOL_LGCN_ROW."""
+    dev = torch.device("cuda:0")
+    rw = float(g11["reg_weight"][0])
+    _, _, g_bpr, g_reg = lp.g4_terms_f64(g4, rw)
+    assert lp.SHARE[0] <= lp.reg_share(g_bpr, g_reg) <= lp.SHARE[1]
+    outs = []
+    for native in (True, False):
+        m = _model(g4, dev, reg_weight=rw)
+        m.NATIVE_STEP = native
+        m.train()
+        loss = m.predict(_batch(g4, dev))
+        loss.backward()
+        outs.append((loss.detach().clone(), m.user_embedding.weight.grad.clone(), m.item_embedding.weight.grad.clone()))
+    assert all(torch.equal(a, b) for a, b in zip(*outs))
+    for native, (loss, gU, gI) in zip((True, False), outs):
+        gU, gI = gU.cpu().numpy(), gI.cpu().numpy()
+        e_loss = abs(float(loss) - float(g11["loss"][0])) / float(g11["loss"][0])
+        eu, ei = rel_err(gU, g11["gU"]), rel_err(gI, g11["gI"])
+        print("g11 native %s: loss err %.2e rel_err users %.2e items %.2e (tol %.0e)" % (native, e_loss, eu, ei, TOL), flush=True)
+        assert e_loss < TOL and eu < TOL and ei < TOL
+        lp.check_rows("g11 native %s" % native, gU, gI, g11["gU"], g11["gI"], lp.TOL_LGCN_ROW, g4["u"], g4["p"], g4["n"])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("D,L,B,max_nnz", lp.STEP_CASES)
+def test_native_step_matches_oracle_and_float64_where_the_reg_term_counts(D, L, B, max_nnz):
+    """hip_ops.lightgcn_step on a 300 x 200 graph (a user linked to every item, an isolated user, a power-law rest) with a
+    skewed batch, at embedding sizes, layer counts, batch sizes and chunk lengths the golden does not have — the last case with
+    two combine levels in the product — and a reg_weight per case at which EmbLoss is about half of the gradient"""
+    from whisprrec_amd import hip_ops
+    dev = torch.device("cuda:0")
+    c = lp.step_case(D, L, B, max_nnz)
+    nU, nI, rw = c["n_users"], c["n_items"], c["reg_weight"]
+    assert lp.SHARE[0] <= c["share"] <= lp.SHARE[1]
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    cptr, crow = hip_ops.spmm_chunks(c["row_ptr"], max_nnz)
+    assert int(np.diff(cptr.numpy()).max()) <= max_nnz
+    csr = (cptr.to(dev), crow.to(dev), t(c["col"]), t(c["val"]))
+    assert hip_ops.spmm_levels_of(csr[1]) == (2 if max_nnz == 4 else 1)
+    loss, grad, err = hip_ops.lightgcn_step(t(c["E0"][:nU]), t(c["E0"][nU:]), csr, L, t(c["u"]), t(c["p"]), t(c["n"]), rw)
+    assert int(err.item()) == 0
+    g = grad.cpu().numpy()
+    loss_orc, g_orc = oracle.lightgcn_loss_grads(nU, nI, c["row_ptr"], c["col"], c["val"], c["E0"], L, rw, c["u"], c["p"], c["n"])
+    want, g64 = c["bpr_loss"] + float(np.float32(rw)) * c["reg_loss"], c["g_bpr"] + c["g_reg"]
+    e_orc, e_64 = abs(float(loss) - loss_orc) / loss_orc, abs(float(loss) - want) / want
+    r_orc = max(rel_err(g[:nU], g_orc[:nU]), rel_err(g[nU:], g_orc[nU:]))
+    r_64 = max(rel_err(g[:nU], g64[:nU]), rel_err(g[nU:], g64[nU:]))
+    print("step D %d L %d B %d max_nnz %d rw %.3g share %.2f: loss err oracle %.2e float64 %.2e, rel_err oracle %.2e float64 %.2e "
+          "(tol %.0e)" % (D, L, B, max_nnz, rw, c["share"], e_orc, e_64, r_orc, r_64, TOL), flush=True)
+    assert e_orc < TOL and e_64 < TOL and r_orc < TOL and r_64 < TOL
+    sq3 = lp.embloss_terms_f64(c["E0"][:nU], c["E0"][nU:], c["u"], c["p"], c["n"], rw)[1]
+    for tag, ref in (("oracle", g_orc), ("float64", g64)):
+        lp.check_rows("step D %d L %d B %d max_nnz %d against %s" % (D, L, B, max_nnz, tag), g[:nU], g[nU:], ref[:nU], ref[nU:],
+                      lp.TOL_LGCN_ROW, c["u"], c["p"], c["n"], sq3=sq3)
 
 
 @pytest.mark.gpu

@@ -8,8 +8,14 @@ import pytest
 
 import oracle
 from conftest import rel_err
+from oracle import lightgcn_parity as lp
 
 TOL = 1e-5
+
+
+@pytest.fixture(scope="module")
+def g11():
+    return oracle.load_golden("g11_lightgcn_reg")
 
 
 def test_g1_forward(g1):
@@ -153,6 +159,24 @@ def test_g4_lightgcn_forward_and_grads(g4):
     assert abs(loss - float(g4["loss"][0])) / abs(float(g4["loss"][0])) < TOL
     assert rel_err(g[:nU], g4["gU"]) < TOL
     assert rel_err(g[nU:], g4["gI"]) < TOL
+
+
+def test_g11_lightgcn_loss_and_grads_where_the_reg_term_counts(g4, g11):
+    """g4's inputs at a reg_weight where EmbLoss is about half of the gradient (at g4's own 1e-5 it is 2e-6 of it and the
+    assertions above cannot see it): the bound of this file, and per row the bound derived in oracle/lightgcn_parity.py"""
+    nU, nI, (rp, col, val) = _g4_graph(g4)
+    L, reg = int(g4["hp"][0]), float(g11["reg_weight"][0])
+    E0 = np.concatenate([g4["U0"], g4["I0"]])
+    _, _, g_bpr, g_reg = lp.g4_terms_f64(g4, reg)
+    assert lp.SHARE[0] <= lp.reg_share(g_bpr, g_reg) <= lp.SHARE[1]
+    loss, g = oracle.lightgcn_loss_grads(nU, nI, rp, col, val, E0, L, reg, g4["u"], g4["p"], g4["n"])
+    assert abs(loss - float(g11["loss"][0])) / abs(float(g11["loss"][0])) < TOL
+    assert rel_err(g[:nU], g11["gU"]) < TOL
+    assert rel_err(g[nU:], g11["gI"]) < TOL
+    lp.check_rows("oracle against g11", g[:nU], g[nU:], g11["gU"], g11["gI"], lp.TOL_LGCN_ROW, g4["u"], g4["p"], g4["n"])
+    # the reference in fp32 against the float64 restatement of the two terms: the golden itself is within the same bound
+    lp.check_rows("g11 against float64", g11["gU"], g11["gI"], (g_bpr + g_reg)[:nU], (g_bpr + g_reg)[nU:], lp.TOL_LGCN_ROW,
+                  g4["u"], g4["p"], g4["n"])
 
 
 def test_g4_lightgcn_sgd_3steps(g4):
