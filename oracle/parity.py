@@ -71,6 +71,19 @@ def _row_sums(idx, vals):
     return s[starts], np.add.reduceat(vals[o], starts, axis=0)
 
 
+def bpr_row_grads_f64(U, I, ub, pb, nbk):
+    """float64 BPR loss of one batch (the mean over its triplets) and its gradient by row: (user rows, their gradient sums,
+    item rows, their gradient sums, loss) — rows outside the batch have zero gradient and are not listed"""
+    ue, pe, ne = U[ub], I[pb], I[nbk]
+    x = np.einsum("bd,bd->b", ue, pe) - np.einsum("bd,bd->b", ue, ne)
+    s = 1.0 / (1.0 + np.exp(-x))
+    c = -(s * (1.0 - s) / (GAMMA + s)) / ub.size
+    ru, gu = _row_sums(ub, c[:, None] * (pe - ne))
+    cu = c[:, None] * ue
+    ri, gi = _row_sums(np.concatenate([pb, nbk]), np.concatenate([cu, -cu]))
+    return ru, gu, ri, gi, float(np.mean(-np.log(GAMMA + s)))
+
+
 def bprmf_sgd_f64(U, I, u, p, n, batch, lr, n_steps=None, keep_steps=False):
     """The reference loop's step (src/helpers/BaseRunner.py:194-200 with BPRMF.py:69-80 and loss.py:38; the semantics of
     oracle.bprmf_step_sgd, l2 = 0): strictly sequential batch-synchronous SGD steps, every gradient of a step from the tables
@@ -85,15 +98,7 @@ def bprmf_sgd_f64(U, I, u, p, n, batch, lr, n_steps=None, keep_steps=False):
     losses, kept = np.zeros(nb, np.float64), []
     for k in range(nb):
         ub, pb, nbk = u[k * batch:(k + 1) * batch], p[k * batch:(k + 1) * batch], n[k * batch:(k + 1) * batch]
-        B = ub.size
-        ue, pe, ne = U[ub], I[pb], I[nbk]
-        x = np.einsum("bd,bd->b", ue, pe) - np.einsum("bd,bd->b", ue, ne)
-        s = 1.0 / (1.0 + np.exp(-x))
-        losses[k] = np.mean(-np.log(GAMMA + s))
-        c = -(s * (1.0 - s) / (GAMMA + s)) / B
-        ru, gu = _row_sums(ub, c[:, None] * (pe - ne))
-        cu = c[:, None] * ue
-        ri, gi = _row_sums(np.concatenate([pb, nbk]), np.concatenate([cu, -cu]))
+        ru, gu, ri, gi, losses[k] = bpr_row_grads_f64(U, I, ub, pb, nbk)
         U[ru] -= lr * gu
         I[ri] -= lr * gi
         if keep_steps:

@@ -10,6 +10,7 @@ import torch
 
 import oracle
 from conftest import rel_err
+from oracle import optim_parity
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-5
@@ -86,6 +87,13 @@ def test_sparse_fused_equals_dense_restatement(name, D, zipf):
     Ud, Id, losses, st = outs[0]
     assert rel_err(losses.cpu().numpy(), np.asarray(ref_loss)) < TOL
     assert rel_err(Ud.cpu().numpy(), Uo) < 1e-4 and rel_err(Id.cpu().numpy(), Io) < 1e-4
+    # the same run against float64, measured on the update and on the state (this test's data is optim_parity's regime E)
+    key = {"Adagrad": "E_adagrad_zipf" if zipf else "E_adagrad", "Adadelta": "E_adadelta"}[name]
+    if (name, "E", D, zipf, 0.0) in optim_parity.VARIANTS[key]:
+        c, ref = optim_parity.variant_reference(name, "E", D, zipf, 0.0)
+        assert np.array_equal(c["U0"], U) and np.array_equal(c["u"], u) and np.array_equal(c["p"], p) and np.array_equal(c["n"], n)
+        optim_parity.check_optim_run("%s D=%d fused" % (name, D), ref, Ud, Id, losses, optim_parity.TOL[key],
+                                     optim_parity.state_of(st))
     # rows no batch contains: weights bit-identical (a zero gradient moves nothing)
     mu = np.ones(nU, bool); mu[u] = False
     mi = np.ones(nI, bool); mi[p] = False; mi[n] = False
