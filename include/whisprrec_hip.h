@@ -789,6 +789,47 @@ int32_t wr_infonce_loss_grad(const float *A, const float *Bm, int64_t n_rows, in
                              float tau, float weight, float *loss, int32_t accumulate, float *gA, float *gB,
                              int32_t *err_word, void *workspace, int64_t workspace_bytes, void *stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * K13  One whole SASRec TransformerLayer (src/utils/layers.py:8-86; whisprrec_amd/sasrec.py::_Block), forward and backward,
+ *      fp32.  x, out, grad_out, gx are [B, T, D] row-major.  `params` is a HOST array of 14 device pointers to the live
+ *      parameter storages in _Block.state_dict() order — q / k / v linear (weight [D, D], bias [D]), layer_norm1 (weight,
+ *      bias), linear1 (weight [d_ff, D], bias), linear2 (weight [D, d_ff], bias), layer_norm2 (weight, bias) — read where they
+ *      are: no packing copy.  No output projection, post-norm residuals, LayerNorm eps 1e-5:
+ *   q, k, v = x W^T + b;  S = q k^T / sqrt(D / n_heads) per head, causal mask only (padded positions are ordinary tokens)
+ *   P = softmax(S - m), m the maximum of S over the WHOLE [B, h, T, T] tensor of the call (layers.py:54), not the row's
+ *   A = P v;  C = LN1(drop(A) + x);  out = LN2(drop(relu(C W1^T + b1) W2^T + b2) + C)
+ *   - Zeroed rows: a score row whose exponentials all underflow is 0 / 0 in the reference and set to 0 by its isnan fill
+ *     (:55); here such a row's attention output is 0 as well and the position sees only its residual.
+ *   - Backward: gx and the 14 parameter gradients, packed in gparams in the same order (5 D^2 + 9 D floats, every block
+ *     starts at a multiple of D floats); fully written.  The path through the maximum m is ignored: softmax is
+ *     shift-invariant, that path sums to zero in exact arithmetic.  DEVIATION: a zeroed row passes no gradient through its
+ *     scores, where the reference's autograd yields NaN gradients; that regime is outside the parity claim.
+ *   - gmax [1] on the device: the forward stores m, the backward of the same call reads it (it recomputes the forward of a
+ *     sequence from x; nothing else is saved).
+ *   - Dropout at two sites (0: after attention, 1: after the feed-forward), active iff training != 0 and p > 0; p in [0, 1).
+ *     Counter-based keep mask with the splitmix64 finaliser mix64 of the negative sampler, never stored:
+ *       key = mix64(seed ^ (site + 1) * 0x9E3779B97F4A7C15);  draw = mix64(key ^ (e * 0xD1B54A32D192ED03 + 1)) >> 40,
+ *       e = (b T + t) D + d;  kept iff draw >= floor(p * 2^24), kept elements scaled by the fp32 1 / (1 - p).
+ *     Same distribution as torch's dropout, not its Philox stream.  The backward must be given the forward's p, seed, training.
+ *   - Determinism: no float atomics.  The maximum is a fold of per-workgroup maxima in index order; parameter gradients go to
+ *     per-workgroup partials that are folded in workgroup order.  Same inputs and seed, same bits — out, gx, gparams.
+ *   - Supported (wr_sasblock_supported): D = d_ff in {32, 64}, n_heads in {1, 2, 4} with D / n_heads >= 8, 1 <= T <= 64;
+ *     B in 1 .. 2^24.  Anything else, a NULL or misaligned (16 B) pointer or a short workspace is refused with WR_E_* before
+ *     anything is launched.
+ *   - workspace >= wr_sasblock_workspace_bytes(B, T, D, d_ff, n_heads), 16-byte aligned: q / k / v of the call (12 B T D bytes)
+ *     plus a fixed number of maxima and gradient partials; never decreases as B or T grow.  The forward and the backward of one
+ *     call may share it with other calls on the same stream.
+ *   - Launches: forward 2 (projections + maxima; the rest), backward 2 (all sequences; fold of the partials).  No allocation,
+ *     no host round trip. */
+int32_t wr_sasblock_supported(int32_t D, int32_t d_ff, int32_t n_heads, int32_t T);
+int64_t wr_sasblock_workspace_bytes(int64_t B, int32_t T, int32_t D, int32_t d_ff, int32_t n_heads);
+int32_t wr_sasblock_fwd(const float *x, int64_t B, int32_t T, int32_t D, int32_t d_ff, int32_t n_heads,
+                        const float *const *params, float p, uint64_t seed, int32_t training, float *out, float *gmax,
+                        void *workspace, int64_t workspace_bytes, void *stream);
+int32_t wr_sasblock_bwd(const float *x, const float *grad_out, int64_t B, int32_t T, int32_t D, int32_t d_ff, int32_t n_heads,
+                        const float *const *params, float p, uint64_t seed, int32_t training, const float *gmax, float *gx,
+                        float *gparams, void *workspace, int64_t workspace_bytes, void *stream);
+
 /* LightGCN.predict's per-batch tail in two launches (src/models/general/LightGCN.py:156-175, src/utils/loss.py:37-39,94-98):
  *   loss[0] = mean_b( -log(1e-10 + sigmoid(<Ua[u_b], Ia[p_b]> - <Ua[u_b], Ia[n_b]>)) )
  *             + reg_weight * (||U0[u]||_F + ||I0[p]||_F + ||I0[n]||_F) / B

@@ -40,6 +40,16 @@ static inline int64_t align_up(int64_t x, int64_t a) { return (x + a - 1) / a * 
 constexpr float kGamma = 1e-10f;  // BPRLoss(gamma=1e-10), reference src/utils/loss.py:33
 constexpr int kBlock = 256;       // 4 waves per workgroup
 
+// ------------------------------------------------------------------------------------------------ counter-based draws
+// splitmix64 finaliser: the one generator of the negative sampler and epoch shuffle (wr_sampler.hip) and of the dropout
+// masks of the SASRec block (wr_sasblock.hip); the tests restate it bit for bit.
+__host__ __device__ __forceinline__ uint64_t mix64(uint64_t x) {
+    x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
+    x ^= x >> 27; x *= 0x94D049BB133111EBull;
+    x ^= x >> 31;
+    return x;
+}
+
 // ------------------------------------------------------------------------------------------------ teams
 // A "team" is T consecutive lanes (T in {1,2,4,8,16}) of one 16-lane DPP row that together hold one
 // embedding row: lane l of the team holds float4 chunks l, l+T, ... (NV chunks).  D = 4*T*NV when the row

@@ -12,13 +12,6 @@
 
 namespace wr {
 
-__host__ __device__ __forceinline__ uint64_t mix64(uint64_t x) {  // splitmix64 finaliser
-    x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
-    x ^= x >> 27; x *= 0x94D049BB133111EBull;
-    x ^= x >> 31;
-    return x;
-}
-
 __host__ __device__ __forceinline__ uint32_t draw_item(uint64_t seed, uint64_t epoch, uint64_t row, uint32_t attempt,
                                                        uint32_t n_items) {
     const uint64_t x = mix64(mix64(seed ^ (epoch * 0x9E3779B97F4A7C15ull)) ^ mix64(row * 0xD1B54A32D192ED03ull + attempt));

@@ -1243,6 +1243,86 @@ def infonce_release_workspaces():
     _INFONCE_WS.clear()
 
 
+# ----------------------------------------------------------------------------------------------- SASRec block (K13)
+SASBLOCK_PARAMS = ("masked_attn_head.q_linear.weight", "masked_attn_head.q_linear.bias", "masked_attn_head.k_linear.weight",
+                   "masked_attn_head.k_linear.bias", "masked_attn_head.v_linear.weight", "masked_attn_head.v_linear.bias",
+                   "layer_norm1.weight", "layer_norm1.bias", "linear1.weight", "linear1.bias", "linear2.weight", "linear2.bias",
+                   "layer_norm2.weight", "layer_norm2.bias")           # _Block.state_dict() order = the order of the C-ABI
+
+
+def sasblock_supports(D, d_ff, n_heads, T):
+    """shapes wr_sasblock_fwd / _bwd take (wr_sasblock_supported)"""
+    return bool(abi.lib().wr_sasblock_supported(int(D), int(d_ff), int(n_heads), int(T)))
+
+
+def sasblock_workspace_bytes(B, T, D, d_ff, n_heads):
+    return abi.check_size(abi.lib().wr_sasblock_workspace_bytes(int(B), int(T), int(D), int(d_ff), int(n_heads)),
+                          "wr_sasblock_workspace_bytes")
+
+
+def _sasblock_call_args(x, params, n_heads):
+    B, T, D = (int(v) for v in x.shape)
+    d_ff = int(params[8].shape[0])
+    shapes = [(D, D), (D,)] * 3 + [(D,), (D,), (d_ff, D), (d_ff,), (D, d_ff), (D,), (D,), (D,)]
+    for t, nm, shp in zip(params, SASBLOCK_PARAMS, shapes):
+        _req(t, torch.float32, nm)
+        if tuple(t.shape) != shp:
+            raise ValueError("%s must be %s (got %s)" % (nm, shp, tuple(t.shape)))
+    if not sasblock_supports(D, d_ff, n_heads, T):
+        raise abi.WhisprRecHipError("sasrec_block does not support D=%d d_ff=%d n_heads=%d T=%d (D = d_ff in {32, 64}, n_heads in "
+                                    "{1, 2, 4} with D / n_heads >= 8, T <= 64)" % (D, d_ff, n_heads, T))
+    ptrs = (ctypes.c_void_p * len(params))(*[t.data_ptr() for t in params])
+    ws = workspace(x.device, "sasblock").get(sasblock_workspace_bytes(B, T, D, d_ff, n_heads))
+    return B, T, D, d_ff, ptrs, ws
+
+
+class _SasBlock(torch.autograd.Function):
+    """wr_sasblock_fwd / wr_sasblock_bwd: saves x and the call's score maximum, nothing else"""
+
+    @staticmethod
+    def forward(ctx, x, n_heads, p, seed, training, *params):
+        x = _req(x.detach().contiguous(), torch.float32, "x", 3)
+        params = [t.detach() for t in params]
+        B, T, D, d_ff, ptrs, ws = _sasblock_call_args(x, params, n_heads)
+        out = torch.empty_like(x)
+        gmax = torch.empty(1, dtype=torch.float32, device=x.device)
+        abi.check(abi.lib().wr_sasblock_fwd(_p(x), B, T, D, d_ff, int(n_heads), _addr(ptrs), float(p), int(seed), int(bool(training)),
+                                            _p(out), _p(gmax), _p(ws), ws.numel(), _stream()), "wr_sasblock_fwd")
+        ctx.save_for_backward(x, gmax, *params)
+        ctx.conf = (int(n_heads), float(p), int(seed), int(bool(training)))
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, gmax = ctx.saved_tensors[:2]
+        params = list(ctx.saved_tensors[2:])
+        n_heads, p, seed, training = ctx.conf
+        grad_out = _req(grad_out.contiguous(), torch.float32, "grad_out", 3)
+        B, T, D, d_ff, ptrs, ws = _sasblock_call_args(x, params, n_heads)
+        gx = torch.empty_like(x)
+        packed = torch.empty(sum(t.numel() for t in params), dtype=torch.float32, device=x.device)
+        abi.check(abi.lib().wr_sasblock_bwd(_p(x), _p(grad_out), B, T, D, d_ff, n_heads, _addr(ptrs), p, seed, training, _p(gmax),
+                                            _p(gx), _p(packed), _p(ws), ws.numel(), _stream()), "wr_sasblock_bwd")
+        views, o = [], 0
+        for t in params:                                  # the packed gradient, returned as views
+            views.append(packed[o:o + t.numel()].view(t.shape))
+            o += t.numel()
+        return (gx, None, None, None, None, *views)
+
+
+def sasblock_params(block):
+    """the 14 parameters of a sasrec._Block in the order of the C-ABI"""
+    sd = dict(block.named_parameters())
+    return [sd[n] for n in SASBLOCK_PARAMS]
+
+
+def sasrec_block(x, block_module, n_heads, p, seed, training):
+    """One whole transformer block of SASRec (sasrec._Block / layers.py:8-86) on x [B, T, D] by the fused HIP kernels, under
+    autograd: two launches forward, two backward.  Dropout p is applied iff `training`, with the counter-based mask of
+    wr_sasblock.hip keyed by `seed` (not torch's generator); the backward recomputes it."""
+    return _SasBlock.apply(x, int(n_heads), float(p), int(seed) & 0xFFFFFFFFFFFFFFFF, bool(training), *sasblock_params(block_module))
+
+
 # ----------------------------------------------------------------------------------------------- optimizers
 def sgd_dense(tab, grad, lr, l2=0.0, stamp=None, step_id=0):
     abi.check(abi.lib().wr_sgd_dense(_p(_req(tab, torch.float32, "tab", 2)), tab.shape[0], tab.shape[1],

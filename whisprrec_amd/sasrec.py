@@ -3,9 +3,14 @@
 In scope for this path: ``item_embedding(padding_idx=0)`` looked up for the history, the positive
 and the negative items (SASRec.py:84,105-106) and the scatter-add of its backward with the padding row's gradient
 dropped.  ``HipEmbedding`` does exactly that through ``wr_gather_rows`` / ``wr_scatter_add_rows`` (sorted, deterministic).
-The single transformer block (src/utils/layers.py:8-86) is dense T<=20 attention and stays on stock PyTorch-ROCm ops; it
-is restated here with the reference's parameter names so checkpoints interchange.
+The transformer block (src/utils/layers.py:8-86) is restated here with the reference's parameter names so checkpoints
+interchange, and has two paths.  ``--block_native 0`` (default): stock PyTorch-ROCm ops under autograd.  ``--block_native 1``:
+each block is one call of ``hip_ops.sasrec_block`` (wr_sasblock.hip, K13) — two launches forward, two backward, in training
+and evaluation alike; its dropout mask is the kernel's own counter-based generator, seeded per step and per layer from
+``--random_seed``.  A shape the kernels do not take is logged once and keeps the stock path.
 """
+import logging
+
 import numpy as np
 import torch
 import torch.nn as nn
@@ -110,6 +115,8 @@ def make_sasrec(sequential_model_cls):
             parser.add_argument("--num_layers", type=int, default=1, help="Number of self-attention layers.")
             parser.add_argument("--num_heads", type=int, default=4, help="Number of attention heads.")
             parser.add_argument("--dropout", type=float, default=0.1, help="Dropout probability.")
+            parser.add_argument("--block_native", type=int, default=0, choices=[0, 1],
+                                help="1: each transformer block by the fused HIP kernels (forward and backward); 0: torch ops + autograd.")
             return sequential_model_cls.parse_model_args(parser)
 
         def __init__(self, args, corpus):
@@ -120,6 +127,22 @@ def make_sasrec(sequential_model_cls):
             self.transformer_block = nn.ModuleList([_Block(self.emb_size, self.emb_size, args.num_heads, args.dropout)
                                                     for _ in range(args.num_layers)])
             self.apply(_xavier_normal_all)
+            self.num_heads, self.dropout = int(args.num_heads), float(args.dropout)
+            self.block_native = bool(int(getattr(args, "block_native", 0)))
+            self._block_native_ok = {}   # per history length, decided at its first batch: the library says what it takes
+            self._block_seed = int(getattr(args, "random_seed", 0)) * 0x9E3779B97F4A7C15
+            self._block_calls = 0        # one dropout stream per training step and layer
+
+        def _use_block_native(self, T):
+            if not self.block_native:
+                return False
+            if T not in self._block_native_ok:
+                ok = hip_ops.sasblock_supports(self.emb_size, self.emb_size, self.num_heads, T)
+                if not ok and not any(v is False for v in self._block_native_ok.values()):
+                    logging.warning("--block_native 1: the block kernels do not take emb_size=%d num_heads=%d history=%d; keeping "
+                                    "the torch path", self.emb_size, self.num_heads, T)
+                self._block_native_ok[T] = ok
+            return self._block_native_ok[T]
 
         def forward(self, feed_dict):
             history, lengths = feed_dict["history_items"], feed_dict["lengths"]
@@ -128,8 +151,13 @@ def make_sasrec(sequential_model_cls):
             pos_ids = torch.arange(T, device=history.device).unsqueeze(0).expand_as(history)
             x = self.item_embedding(history) + self.position_embedding(pos_ids)        # SASRec.py:79-85
             mask = torch.tril(torch.ones(1, 1, T, T, dtype=torch.int32, device=history.device))
-            for blk in self.transformer_block:
-                x = blk(x, mask)
+            if self._use_block_native(T):
+                for blk in self.transformer_block:
+                    x = hip_ops.sasrec_block(x, blk, self.num_heads, self.dropout, self._block_seed + self._block_calls, self.training)
+                    self._block_calls += int(self.training)
+            else:
+                for blk in self.transformer_block:
+                    x = blk(x, mask)
             x = x * valid[:, :, None]
             return x[torch.arange(bsz, device=history.device), lengths - 1, :]          # last valid position (:95)
 
