@@ -753,6 +753,36 @@ int32_t wr_topk_recommend(const float *user_mat, int64_t n_user_rows, const floa
                           void *stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * K14  Ranking evaluation and top-K with one query vector PER ROW — sequential models (SASRec: the query of row e is
+ *      the encoder's output for row e's own history, BaseRunner.py:229-236 over SASRec.full_predict), where the row that
+ *      scores and the row that masks are two different things:
+ *   score(e, j)     = <query_mat[q(e)], item_tab[j]>,   q(e) = query_row[e], or e itself when query_row is NULL
+ *   mask of row e   = the list of row mask_row[e] of the CSR mask_ptr int64 [n_mask_rows+1] / mask_idx int32 (ascending
+ *                     per list) — the user of row e; several rows may share one list
+ *   wr_rank_eval_rows:       rank[e] = 1 + #{ j not masked for e : score(e, j) > target_score[e] },
+ *                            target_score[e] = score(e, eval_target[e])                          (as wr_rank_eval, K10)
+ *   wr_topk_recommend_rows:  the k best unmasked items of every row                            (as wr_topk_recommend, K11)
+ *   - Same kernels as K10 / K11 (those entries pass their one index array for both roles): the same fp32 k-ordered
+ *     v_mfma_f32_32x32x2_f32 chain, so with query_mat[q(e)] = user_mat[u] and mask_row[e] = u every output is bitwise that of
+ *     wr_rank_eval / wr_topk_recommend, and a returned top-K score is bitwise the target_score of that (row, item) pair.
+ *   - mask_row, mask_ptr and mask_idx are all NULL (no mask) or all non-NULL.  query_row == NULL requires n <= n_query_rows.
+ *   - D: the set wr_rank_eval / wr_topk_supported take.  Workspace of the top-K entry: wr_topk_workspace_bytes(n, n_items,
+ *     D, k) as it is (it depends on nothing else).  Order, ties and padding of the top-K entry: score descending, then item
+ *     id ascending, then -1 / -inf.
+ *   - Ids (query_row, eval_target, mask_row) are trusted exactly as wr_rank_eval trusts eval_user and eval_target: they are
+ *     not range-checked on the device, the caller passes ids inside [0, n_query_rows), [0, n_items), [0, n_mask_rows).
+ *   - Argument errors (WR_E_*) are reported before anything is launched.
+ * --------------------------------------------------------------------------------------------------- */
+int32_t wr_rank_eval_rows(const float *query_mat, int64_t n_query_rows, const float *item_tab, int64_t n_items, int32_t D,
+                          const int64_t *query_row /* NULL: row e */, const int64_t *eval_target, int64_t n,
+                          const int64_t *mask_row, int64_t n_mask_rows, const int64_t *mask_ptr, const int32_t *mask_idx,
+                          int32_t *rank, float *target_score, void *stream);
+int32_t wr_topk_recommend_rows(const float *query_mat, int64_t n_query_rows, const float *item_tab, int64_t n_items, int32_t D,
+                               const int64_t *query_row /* NULL: row e */, int64_t n, const int64_t *mask_row,
+                               int64_t n_mask_rows, const int64_t *mask_ptr, const int32_t *mask_idx, int32_t k,
+                               int32_t *out_item, float *out_score, void *workspace, int64_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * K12  InfoNCE loss and gradient of ONE side (users or items) of SGL's calc_ssl_loss (src/models/general/SGL.py:196-230,
  *      the formula at :213-220), without the [B, n_rows] score matrix.  A = view 1, Bm = view 2, both [n_rows, D] fp32
  *      row-major; idx int64 [B], duplicates allowed:

@@ -170,10 +170,13 @@ SIGNATURES = {
     "wr_spmm_csr_chunked_modes": (c_i32, [c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "wr_axpy": (c_i32, [c_vp, c_vp, c_i64, c_f32, c_i32, c_vp]),
     "wr_rank_eval": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i32, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "wr_rank_eval_rows": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i32, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "wr_topk_supported": (c_i32, [c_i32, c_i32]),
     "wr_topk_workspace_bytes": (c_i64, [c_i64, c_i64, c_i32, c_i32]),
     "wr_topk_recommend": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i32, c_vp, c_i64, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_i64,
                                   c_vp]),
+    "wr_topk_recommend_rows": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i32, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp,
+                                       c_i64, c_vp]),
     "wr_infonce_supported": (c_i32, [c_i32]),
     "wr_infonce_workspace_bytes": (c_i64, [c_i64, c_i64, c_i32]),
     "wr_infonce_loss_grad": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_vp, c_i64, c_f32, c_f32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp,

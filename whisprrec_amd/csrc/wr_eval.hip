@@ -16,13 +16,13 @@ namespace wr {
 
 constexpr int kEvalChunk = 2048; // items per workgroup along grid.y
 
-// score of the ground-truth item, as the k-ordered fmaf chain the MFMA accumulates
+// score of the ground-truth item, as the k-ordered fmaf chain the MFMA accumulates; qrows NULL: row i is its own query
 __global__ __launch_bounds__(kBlock) void eval_target_kernel(const float *__restrict__ U, const float *__restrict__ I, int D,
-                                                              const int64_t *__restrict__ eu, const int64_t *__restrict__ et,
+                                                              const int64_t *__restrict__ qrows, const int64_t *__restrict__ et,
                                                               int64_t n, float *__restrict__ tscore) {
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i >= n) return;
-    const float *a = U + eu[i] * (int64_t)D, *b = I + et[i] * (int64_t)D;
+    const float *a = U + (qrows != nullptr ? qrows[i] : i) * (int64_t)D, *b = I + et[i] * (int64_t)D;
     float s = 0.f;
     for (int k = 0; k < D; ++k) s = fmaf(a[k], b[k], s);
     tscore[i] = s;
@@ -84,12 +84,13 @@ struct RankCount {
 
 // D outside {8, 16, 32, 64}: the LDS-operand scan
 __global__ __launch_bounds__(kBlock) void eval_rank_kernel(const float *__restrict__ U, const float *__restrict__ I, int D,
-                                                            int64_t n_items, const int64_t *__restrict__ eu,
+                                                            int64_t n_items, const int64_t *__restrict__ qrows,
+                                                            const int64_t *__restrict__ mrows,
                                                             const float *__restrict__ tscore, int64_t n,
                                                             const int64_t *__restrict__ mask_ptr, const int *__restrict__ mask_idx,
                                                             int *__restrict__ rank_cnt) {
     RankCount count(tscore, n, n_items);
-    score_scan_lds(U, I, D, n_items, eu, n, mask_ptr, mask_idx, (int64_t)blockIdx.y * kEvalChunk, kEvalChunk, count);
+    score_scan_lds(U, I, D, n_items, qrows, mrows, n, mask_ptr, mask_idx, (int64_t)blockIdx.y * kEvalChunk, kEvalChunk, count);
     count.flush(rank_cnt);
 }
 
@@ -97,12 +98,13 @@ __global__ __launch_bounds__(kBlock) void eval_rank_kernel(const float *__restri
 // 3 workgroups per CU (<= 168 VGPRs, no spill): A/B on MI355X 2 / 3 / 4 per CU = 101 / 111 / 86 TFLOP/s at 100K x 100K x 64.
 template <int KS>
 __global__ __launch_bounds__(kBlock, 3) void eval_rank_kernel_rega(const float *__restrict__ U, const float *__restrict__ I,
-                                                                 int64_t n_items, const int64_t *__restrict__ eu,
+                                                                 int64_t n_items, const int64_t *__restrict__ qrows,
+                                                                 const int64_t *__restrict__ mrows,
                                                                  const float *__restrict__ tscore, int64_t n,
                                                                  const int64_t *__restrict__ mask_ptr,
                                                                  const int *__restrict__ mask_idx, int *__restrict__ rank_cnt) {
     RankCount count(tscore, n, n_items);
-    score_scan_rega<KS>(U, I, n_items, eu, n, mask_ptr, mask_idx, (int64_t)blockIdx.y * kEvalChunk, kEvalChunk, count);
+    score_scan_rega<KS>(U, I, n_items, qrows, mrows, n, mask_ptr, mask_idx, (int64_t)blockIdx.y * kEvalChunk, kEvalChunk, count);
     count.flush(rank_cnt);
 }
 
@@ -110,6 +112,42 @@ __global__ __launch_bounds__(kBlock) void eval_finish_kernel(int *__restrict__ r
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i < n) rank[i] += 1;
 }
+
+// The launches behind wr_rank_eval and wr_rank_eval_rows; arguments are checked by the entries.
+static int32_t rank_eval_launch(const float *query_mat, const float *item_tab, int64_t n_items, int32_t D, const int64_t *qrows,
+                                const int64_t *mrows, const int64_t *eval_target, int64_t n, const int64_t *mask_ptr,
+                                const int32_t *mask_idx, int32_t *rank, float *target_score, hipStream_t stream) {
+    WR_HIP(hipMemsetAsync(rank, 0, (size_t)n * 4, stream));
+    hipLaunchKernelGGL(eval_target_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, query_mat, item_tab,
+                       D, qrows, eval_target, n, target_score);
+    WR_LAUNCH_CHECK("eval_target_kernel");
+    const dim3 grid((unsigned)((n + kScoreRows - 1) / kScoreRows), (unsigned)((n_items + kEvalChunk - 1) / kEvalChunk));
+    if (score_rega_d(D)) {   // A operand in registers, double-buffered item tiles
+#define WR_EVAL_REGA(KS_)                                                                                             \
+    hipLaunchKernelGGL(eval_rank_kernel_rega<KS_>, grid, dim3(kBlock), 0, stream, query_mat, item_tab, n_items, qrows, mrows, \
+                       target_score, n, mask_ptr, mask_idx, rank)
+        WR_DISPATCH_KS(D, 4, 32, WR_EVAL_REGA);
+#undef WR_EVAL_REGA
+    } else {
+        const size_t lds = score_lds_bytes(D, 1);
+        if (lds > 64 * 1024)
+            WR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(eval_rank_kernel),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(eval_rank_kernel, grid, dim3(kBlock), lds, stream, query_mat, item_tab, D, n_items, qrows, mrows,
+                           target_score, n, mask_ptr, mask_idx, rank);
+    }
+    WR_LAUNCH_CHECK("eval_rank_kernel");
+    hipLaunchKernelGGL(eval_finish_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, rank, n);
+    WR_LAUNCH_CHECK("eval_finish_kernel");
+    return WR_OK;
+}
+
+// D outside {8,16,32,64}: the LDS-operand kernel stages (128 + 32) rows of D + 1 floats + 128 bitmap words; a
+// workgroup gets at most 160 KiB (163,840 B) on gfx950 -> D <= 252
+#define WR_EVAL_REQUIRE_D(D_)                                                                                          \
+    WR_REQUIRE(score_rega_d(D_) || score_lds_bytes(D_, 1) <= kLdsPerWorkgroup, WR_E_RANGE,                             \
+               "rank_eval supports D <= 252 (LDS staging: %lld B needed, 163840 B per workgroup); got D=%d",           \
+               (long long)score_lds_bytes(D_, 1), D_)
 
 }  // namespace wr
 
@@ -126,37 +164,31 @@ int32_t wr_rank_eval(const float *user_mat, int64_t n_user_rows, const float *it
     WR_REQUIRE(eval_user && eval_target && rank && target_score, WR_E_NULL, "rank_eval: NULL argument");
     WR_REQUIRE((mask_ptr == nullptr) == (mask_idx == nullptr), WR_E_NULL, "rank_eval: mask_ptr and mask_idx go together");
     WR_REQUIRE(n >= 0 && n < (int64_t(1) << 31), WR_E_SHAPE, "rank_eval: n out of range");
-    // D outside {8,16,32,64}: the LDS-operand kernel stages (128 + 32) rows of D + 1 floats + 128 bitmap words; a
-    // workgroup gets at most 160 KiB (163,840 B) on gfx950 -> D <= 252
-    const size_t lds_generic = score_lds_bytes(D, 1);
-    WR_REQUIRE(score_rega_d(D) || lds_generic <= kLdsPerWorkgroup, WR_E_RANGE,
-               "rank_eval supports D <= 252 (LDS staging: %lld B needed, 163840 B per workgroup); got D=%d",
-               (long long)lds_generic, D);
+    WR_EVAL_REQUIRE_D(D);
     if (n == 0) return WR_OK;
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    WR_HIP(hipMemsetAsync(rank, 0, (size_t)n * 4, stream));
-    hipLaunchKernelGGL(eval_target_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, user_mat, item_tab,
-                       D, eval_user, eval_target, n, target_score);
-    WR_LAUNCH_CHECK("eval_target_kernel");
-    const dim3 grid((unsigned)((n + kScoreRows - 1) / kScoreRows), (unsigned)((n_items + kEvalChunk - 1) / kEvalChunk));
-    if (score_rega_d(D)) {   // A operand in registers, double-buffered item tiles
-#define WR_EVAL_REGA(KS_)                                                                                             \
-    hipLaunchKernelGGL(eval_rank_kernel_rega<KS_>, grid, dim3(kBlock), 0, stream, user_mat, item_tab, n_items, eval_user, \
-                       target_score, n, mask_ptr, mask_idx, rank)
-        WR_DISPATCH_KS(D, 4, 32, WR_EVAL_REGA);
-#undef WR_EVAL_REGA
-    } else {
-        const size_t lds = lds_generic;
-        if (lds > 64 * 1024)
-            WR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(eval_rank_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(eval_rank_kernel, grid, dim3(kBlock), lds, stream, user_mat, item_tab, D, n_items, eval_user,
-                           target_score, n, mask_ptr, mask_idx, rank);
-    }
-    WR_LAUNCH_CHECK("eval_rank_kernel");
-    hipLaunchKernelGGL(eval_finish_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, rank, n);
-    WR_LAUNCH_CHECK("eval_finish_kernel");
-    return WR_OK;
+    return rank_eval_launch(user_mat, item_tab, n_items, D, eval_user, eval_user, eval_target, n, mask_ptr, mask_idx, rank,
+                            target_score, reinterpret_cast<hipStream_t>(stream_));
+}
+
+int32_t wr_rank_eval_rows(const float *query_mat, int64_t n_query_rows, const float *item_tab, int64_t n_items, int32_t D,
+                          const int64_t *query_row, const int64_t *eval_target, int64_t n, const int64_t *mask_row,
+                          int64_t n_mask_rows, const int64_t *mask_ptr, const int32_t *mask_idx, int32_t *rank,
+                          float *target_score, void *stream_) {
+    int32_t rc;
+    if ((rc = check_table(query_mat, n_query_rows, D, "query_mat")) != WR_OK) return rc;
+    if ((rc = check_table(item_tab, n_items, D, "item_tab")) != WR_OK) return rc;
+    WR_REQUIRE(eval_target && rank && target_score, WR_E_NULL, "rank_eval_rows: NULL argument");
+    WR_REQUIRE((mask_ptr == nullptr) == (mask_idx == nullptr) && (mask_ptr == nullptr) == (mask_row == nullptr), WR_E_NULL,
+               "rank_eval_rows: mask_row, mask_ptr and mask_idx go together");
+    WR_REQUIRE(n >= 0 && n < (int64_t(1) << 31), WR_E_SHAPE, "rank_eval_rows: n out of range");
+    WR_REQUIRE(query_row != nullptr || n <= n_query_rows, WR_E_SHAPE,
+               "rank_eval_rows: n=%lld rows but query_mat has %lld and no query_row is given", (long long)n, (long long)n_query_rows);
+    WR_REQUIRE(mask_ptr == nullptr || n_mask_rows >= 1, WR_E_SHAPE, "rank_eval_rows: n_mask_rows=%lld with a mask",
+               (long long)n_mask_rows);
+    WR_EVAL_REQUIRE_D(D);
+    if (n == 0) return WR_OK;
+    return rank_eval_launch(query_mat, item_tab, n_items, D, query_row, mask_row, eval_target, n, mask_ptr, mask_idx, rank,
+                            target_score, reinterpret_cast<hipStream_t>(stream_));
 }
 
 }  // extern "C"

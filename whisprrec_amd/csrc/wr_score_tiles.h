@@ -8,6 +8,9 @@
 //                    kScoreTile rows are double-buffered in LDS (the next tile's global loads fly while the current one
 //                    feeds the matrix cores), one barrier per tile
 //   score_scan_lds   any other D: the rows and one tile of kScoreTileG items in dynamic LDS, two barriers per tile
+// Both take two row arrays, because a row has two roles that sequential models keep apart: qrows[e] is the row of the
+// query matrix that row e scores with (NULL: row e itself), mrows[e] the row of the mask CSR that hides items from it (read
+// only when a mask is given).  Factor models pass their user ids for both.
 // Consumer contract (both scans), consume(acc, j0, plain, masked):
 //   acc[c][reg]      score of row acc_row(reg, lane >> 5) of the wave's slab against item j0 + 32 c + (lane & 31)
 //   plain            wave-uniform.  True: no row of the slab has a masked item in the tile and the whole tile lies inside
@@ -68,12 +71,12 @@ struct MaskCursor {
     int64_t cur = 0, cend = 0;
     int nxt = 0x7fffffff;
 
-    // positioned at the first masked item >= c0 of row e (user rows[e]); no list, or e >= n: an empty one
+    // positioned at the first masked item >= c0 of row e (mask row mrows[e]); no list, or e >= n: an empty one
     __device__ __forceinline__ MaskCursor(const int64_t *__restrict__ mask_ptr, const int *__restrict__ mask_idx,
-                                          const int64_t *__restrict__ rows, int64_t e, int64_t n, int64_t c0)
+                                          const int64_t *__restrict__ mrows, int64_t e, int64_t n, int64_t c0)
         : idx(mask_idx) {
         if (threadIdx.x < kScoreRows && mask_ptr != nullptr && e < n) {
-            const int64_t uu = rows[e];
+            const int64_t uu = mrows[e];
             int64_t lo = mask_ptr[uu], hi = mask_ptr[uu + 1];
             cend = hi;
             while (lo < hi) {
@@ -146,13 +149,15 @@ __device__ __forceinline__ void score_tile_lds(const float *arow, const float *b
     for (int k0 = 0; k0 < D; k0 += 2) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(arow[k0], brow[k0], acc, 0, 0, 0);
 }
 
-// Register-operand scan of the items c0 .. min(c0 + chunk, n_items) - 1 against the rows U[rows[e]], e = blockIdx.x *
-// kScoreRows + 0..127 (e < n).  Static LDS: 2 tiles, 2 x 2 x 128 bitmap words, 2 x 4 slab flags.
+// Register-operand scan of the items c0 .. min(c0 + chunk, n_items) - 1 against the rows U[qrows[e]] (qrows NULL: U[e]),
+// e = blockIdx.x * kScoreRows + 0..127 (e < n), masked by the lists of mrows[e].
+// Static LDS: 2 tiles, 2 x 2 x 128 bitmap words, 2 x 4 slab flags.
 template <int KS, typename Consumer>
 __device__ __forceinline__ void score_scan_rega(const float *__restrict__ U, const float *__restrict__ I, int64_t n_items,
-                                                const int64_t *__restrict__ rows, int64_t n,
-                                                const int64_t *__restrict__ mask_ptr, const int *__restrict__ mask_idx,
-                                                int64_t c0, int64_t chunk, Consumer &&consume) {
+                                                const int64_t *__restrict__ qrows, const int64_t *__restrict__ mrows,
+                                                int64_t n, const int64_t *__restrict__ mask_ptr,
+                                                const int *__restrict__ mask_idx, int64_t c0, int64_t chunk,
+                                                Consumer &&consume) {
     constexpr int D = 2 * KS, LDW = D + 1, C = kScoreTile / 32;
     __shared__ float it[2][kScoreTile * LDW];
     __shared__ unsigned rowmask[2][C][kScoreRows];
@@ -165,11 +170,11 @@ __device__ __forceinline__ void score_scan_rega(const float *__restrict__ U, con
     float a[KS];
     {
         const int64_t e = e0 + wave * 32 + col;
-        const float *urow = U + ((e < n) ? rows[e] : 0) * (int64_t)D + half;
+        const float *urow = U + ((e < n) ? (qrows != nullptr ? qrows[e] : e) : 0) * (int64_t)D + half;
 #pragma unroll
         for (int s = 0; s < KS; ++s) a[s] = (e < n) ? urow[2 * s] : 0.f;
     }
-    MaskCursor cursor(mask_ptr, mask_idx, rows, e0 + threadIdx.x, n, c0);
+    MaskCursor cursor(mask_ptr, mask_idx, mrows, e0 + threadIdx.x, n, c0);
     TileStager<D, kScoreTile> stager;
     auto deposit = [&](int buf, int64_t j0) {
         stager.deposit(it[buf]);
@@ -201,9 +206,10 @@ __device__ __forceinline__ void score_scan_rega(const float *__restrict__ U, con
 // consumer sets up before the call is visible to all waves at the first tile.
 template <typename Consumer>
 __device__ __forceinline__ void score_scan_lds(const float *__restrict__ U, const float *__restrict__ I, int D, int64_t n_items,
-                                               const int64_t *__restrict__ rows, int64_t n,
-                                               const int64_t *__restrict__ mask_ptr, const int *__restrict__ mask_idx,
-                                               int64_t c0, int64_t chunk, Consumer &&consume) {
+                                               const int64_t *__restrict__ qrows, const int64_t *__restrict__ mrows,
+                                               int64_t n, const int64_t *__restrict__ mask_ptr,
+                                               const int *__restrict__ mask_idx, int64_t c0, int64_t chunk,
+                                               Consumer &&consume) {
     extern __shared__ float lds[];
     const int ldw = D + 1;
     float *ue = lds;                                                    // [kScoreRows][ldw]
@@ -216,9 +222,9 @@ __device__ __forceinline__ void score_scan_lds(const float *__restrict__ U, cons
     for (int idx = threadIdx.x; idx < kScoreRows * D; idx += kBlock) {
         const int r = idx / D, k = idx - r * D;
         const int64_t e = e0 + r;
-        ue[r * ldw + k] = (e < n) ? U[rows[e] * (int64_t)D + k] : 0.f;
+        ue[r * ldw + k] = (e < n) ? U[(qrows != nullptr ? qrows[e] : e) * (int64_t)D + k] : 0.f;
     }
-    MaskCursor cursor(mask_ptr, mask_idx, rows, e0 + threadIdx.x, n, c0);
+    MaskCursor cursor(mask_ptr, mask_idx, mrows, e0 + threadIdx.x, n, c0);
     const float *arow = ue + (wave * 32 + col) * ldw + half;            // A[i = lane&31][k = lane>>5]
     const float *brow = it + col * ldw + half;                          // B[k = lane>>5][j = lane&31]
     for (int64_t j0 = c0; j0 < c1; j0 += kScoreTileG) {

@@ -217,14 +217,15 @@ __device__ __forceinline__ void topk_absorb(const TopkRows &w, const f32x16 (&ac
 // 2 workgroups per CU: at 3 (<= 168 VGPRs) the staging and merge path spills to scratch.
 template <int KS, int E>
 __global__ __launch_bounds__(kBlock, 2) void topk_scan_kernel_rega(const float *__restrict__ U, const float *__restrict__ I,
-                                                                 int64_t n_items, const int64_t *__restrict__ qu, int64_t n,
+                                                                 int64_t n_items, const int64_t *__restrict__ qrows,
+                                                                 const int64_t *__restrict__ mrows, int64_t n,
                                                                  const int64_t *__restrict__ mask_ptr,
                                                                  const int *__restrict__ mask_idx, int k, int64_t chunk,
                                                                  int nc, u64 *ws) {
     __shared__ __attribute__((aligned(16))) unsigned thr_s[kScoreRows];
     __shared__ int cnt_s[kScoreRows];
     const TopkRows w = topk_rows<E>(ws, nc, k, kScoreTile, n, thr_s, cnt_s);
-    score_scan_rega<KS>(U, I, n_items, qu, n, mask_ptr, mask_idx, (int64_t)blockIdx.y * chunk, chunk,
+    score_scan_rega<KS>(U, I, n_items, qrows, mrows, n, mask_ptr, mask_idx, (int64_t)blockIdx.y * chunk, chunk,
                         [&](const auto &acc, int64_t j0, bool plain, auto masked) {
                             topk_absorb<E>(w, acc, j0, plain, n_items, masked);
                         });
@@ -235,14 +236,15 @@ __global__ __launch_bounds__(kBlock, 2) void topk_scan_kernel_rega(const float *
 // LDS-operand kernel for any other D (multiple of 4, <= 252); thresholds and counts are the scan's side words.
 template <int E>
 __global__ __launch_bounds__(kBlock) void topk_scan_kernel(const float *__restrict__ U, const float *__restrict__ I, int D,
-                                                           int64_t n_items, const int64_t *__restrict__ qu, int64_t n,
+                                                           int64_t n_items, const int64_t *__restrict__ qrows,
+                                                           const int64_t *__restrict__ mrows, int64_t n,
                                                            const int64_t *__restrict__ mask_ptr,
                                                            const int *__restrict__ mask_idx, int k, int64_t chunk, int nc,
                                                            u64 *ws) {
     unsigned *thr_s = score_lds_side(D);                                // [kScoreRows]
     int *cnt_s = reinterpret_cast<int *>(thr_s + kScoreRows);           // [kScoreRows]
     const TopkRows w = topk_rows<E>(ws, nc, k, kScoreTileG, n, thr_s, cnt_s);
-    score_scan_lds(U, I, D, n_items, qu, n, mask_ptr, mask_idx, (int64_t)blockIdx.y * chunk, chunk,
+    score_scan_lds(U, I, D, n_items, qrows, mrows, n, mask_ptr, mask_idx, (int64_t)blockIdx.y * chunk, chunk,
                    [&](const auto &acc, int64_t j0, bool plain, auto masked) {
                        topk_absorb<E>(w, acc, j0, plain, n_items, masked);
                    });
@@ -313,6 +315,47 @@ static inline int64_t topk_chunks(int64_t n, int64_t n_items) {
     return best;
 }
 
+// The launches behind wr_topk_recommend and wr_topk_recommend_rows; arguments are checked by the entries.
+static int32_t topk_launch(const float *query_mat, const float *item_tab, int64_t n_items, int32_t D, const int64_t *qrows,
+                           const int64_t *mrows, int64_t n, const int64_t *mask_ptr, const int32_t *mask_idx, int32_t k,
+                           int32_t *out_item, float *out_score, void *workspace, hipStream_t stream) {
+    u64 *ws = reinterpret_cast<u64 *>(workspace);
+    const int64_t tiles = (n_items + kScoreTile - 1) / kScoreTile;
+    int64_t nc = topk_chunks(n, n_items);
+    const int64_t chunk = (tiles + nc - 1) / nc * kScoreTile;     // whole tiles of both kernels
+    nc = (n_items + chunk - 1) / chunk;
+    const dim3 grid((unsigned)((n + kScoreRows - 1) / kScoreRows), (unsigned)nc);
+    const bool big = k > 128;
+    const int nci = (int)nc;
+    if (score_rega_d(D)) {
+#define WR_TOPK_REGA(KS_, E_)                                                                                            \
+    hipLaunchKernelGGL((topk_scan_kernel_rega<KS_, E_>), grid, dim3(kBlock), 0, stream, query_mat, item_tab, n_items, qrows, \
+                       mrows, n, mask_ptr, mask_idx, k, chunk, nci, ws)
+#define WR_TOPK_REGA_K(KS_) do { if (big) WR_TOPK_REGA(KS_, 8); else WR_TOPK_REGA(KS_, 4); } while (0)
+        WR_DISPATCH_KS(D, 4, 32, WR_TOPK_REGA_K);
+#undef WR_TOPK_REGA_K
+#undef WR_TOPK_REGA
+    } else {
+        const size_t lds = topk_lds_generic(D);
+        const void *fn = big ? reinterpret_cast<const void *>(topk_scan_kernel<8>) : reinterpret_cast<const void *>(topk_scan_kernel<4>);
+        if (lds > 64 * 1024) WR_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        if (big)
+            hipLaunchKernelGGL(topk_scan_kernel<8>, grid, dim3(kBlock), lds, stream, query_mat, item_tab, D, n_items, qrows, mrows,
+                               n, mask_ptr, mask_idx, k, chunk, nci, ws);
+        else
+            hipLaunchKernelGGL(topk_scan_kernel<4>, grid, dim3(kBlock), lds, stream, query_mat, item_tab, D, n_items, qrows, mrows,
+                               n, mask_ptr, mask_idx, k, chunk, nci, ws);
+    }
+    WR_LAUNCH_CHECK("topk_scan_kernel");
+    const dim3 mgrid((unsigned)((n + kBlock / 64 - 1) / (kBlock / 64)));
+    if (big)
+        hipLaunchKernelGGL(topk_merge_kernel<8>, mgrid, dim3(kBlock), 0, stream, ws, n, nci, k, out_item, out_score);
+    else
+        hipLaunchKernelGGL(topk_merge_kernel<4>, mgrid, dim3(kBlock), 0, stream, ws, n, nci, k, out_item, out_score);
+    WR_LAUNCH_CHECK("topk_merge_kernel");
+    return WR_OK;
+}
+
 }  // namespace wr
 
 using namespace wr;
@@ -338,6 +381,21 @@ int64_t wr_topk_workspace_bytes(int64_t n, int64_t n_items, int32_t D, int32_t k
     return regions * topk_region(k) * 8 + 256;
 }
 
+// the checks both recommend entries share; `entry` starts the message
+static int32_t topk_check(const char *entry, int64_t n, int64_t n_items, int32_t D, int32_t k, const void *workspace,
+                          int64_t workspace_bytes) {
+    WR_REQUIRE(n >= 0 && n < (int64_t(1) << 31), WR_E_SHAPE, "%s: n out of range", entry);
+    WR_REQUIRE(k >= 1 && k <= 256, WR_E_RANGE, "%s: k=%d must be in [1, 256]", entry, k);
+    WR_REQUIRE(wr_topk_supported(D, k), WR_E_RANGE,
+               "%s supports D in {8,16,32,64} or a multiple of 4 up to 252 (LDS staging: %lld B needed, "
+               "163840 B per workgroup); got D=%d", entry, (long long)topk_lds_generic(D), D);
+    const int64_t need = wr_topk_workspace_bytes(n, n_items, D, k);
+    WR_REQUIRE(workspace != nullptr && workspace_bytes >= need, WR_E_WORKSPACE,
+               "%s: workspace of %lld B, %lld B needed", entry, (long long)workspace_bytes, (long long)need);
+    WR_REQUIRE(aligned16(workspace), WR_E_ALIGN, "%s: workspace is not 16-byte aligned", entry);
+    return WR_OK;
+}
+
 int32_t wr_topk_recommend(const float *user_mat, int64_t n_user_rows, const float *item_tab, int64_t n_items, int32_t D,
                           const int64_t *query_user, int64_t n, const int64_t *mask_ptr, const int32_t *mask_idx,
                           int32_t k, int32_t *out_item, float *out_score, void *workspace, int64_t workspace_bytes,
@@ -347,52 +405,31 @@ int32_t wr_topk_recommend(const float *user_mat, int64_t n_user_rows, const floa
     if ((rc = check_table(item_tab, n_items, D, "item_tab")) != WR_OK) return rc;
     WR_REQUIRE(query_user && out_item && out_score, WR_E_NULL, "topk_recommend: NULL argument");
     WR_REQUIRE((mask_ptr == nullptr) == (mask_idx == nullptr), WR_E_NULL, "topk_recommend: mask_ptr and mask_idx go together");
-    WR_REQUIRE(n >= 0 && n < (int64_t(1) << 31), WR_E_SHAPE, "topk_recommend: n out of range");
-    WR_REQUIRE(k >= 1 && k <= 256, WR_E_RANGE, "topk_recommend: k=%d must be in [1, 256]", k);
-    WR_REQUIRE(wr_topk_supported(D, k), WR_E_RANGE,
-               "topk_recommend supports D in {8,16,32,64} or a multiple of 4 up to 252 (LDS staging: %lld B needed, "
-               "163840 B per workgroup); got D=%d", (long long)topk_lds_generic(D), D);
-    const int64_t need = wr_topk_workspace_bytes(n, n_items, D, k);
-    WR_REQUIRE(workspace != nullptr && workspace_bytes >= need, WR_E_WORKSPACE,
-               "topk_recommend: workspace of %lld B, %lld B needed", (long long)workspace_bytes, (long long)need);
-    WR_REQUIRE(aligned16(workspace), WR_E_ALIGN, "topk_recommend: workspace is not 16-byte aligned");
+    if ((rc = topk_check("topk_recommend", n, n_items, D, k, workspace, workspace_bytes)) != WR_OK) return rc;
     if (n == 0) return WR_OK;
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    u64 *ws = reinterpret_cast<u64 *>(workspace);
-    const int64_t tiles = (n_items + kScoreTile - 1) / kScoreTile;
-    int64_t nc = topk_chunks(n, n_items);
-    const int64_t chunk = (tiles + nc - 1) / nc * kScoreTile;     // whole tiles of both kernels
-    nc = (n_items + chunk - 1) / chunk;
-    const dim3 grid((unsigned)((n + kScoreRows - 1) / kScoreRows), (unsigned)nc);
-    const bool big = k > 128;
-    const int nci = (int)nc;
-    if (score_rega_d(D)) {
-#define WR_TOPK_REGA(KS_, E_)                                                                                            \
-    hipLaunchKernelGGL((topk_scan_kernel_rega<KS_, E_>), grid, dim3(kBlock), 0, stream, user_mat, item_tab, n_items, \
-                       query_user, n, mask_ptr, mask_idx, k, chunk, nci, ws)
-#define WR_TOPK_REGA_K(KS_) do { if (big) WR_TOPK_REGA(KS_, 8); else WR_TOPK_REGA(KS_, 4); } while (0)
-        WR_DISPATCH_KS(D, 4, 32, WR_TOPK_REGA_K);
-#undef WR_TOPK_REGA_K
-#undef WR_TOPK_REGA
-    } else {
-        const size_t lds = topk_lds_generic(D);
-        const void *fn = big ? reinterpret_cast<const void *>(topk_scan_kernel<8>) : reinterpret_cast<const void *>(topk_scan_kernel<4>);
-        if (lds > 64 * 1024) WR_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        if (big)
-            hipLaunchKernelGGL(topk_scan_kernel<8>, grid, dim3(kBlock), lds, stream, user_mat, item_tab, D, n_items, query_user,
-                               n, mask_ptr, mask_idx, k, chunk, nci, ws);
-        else
-            hipLaunchKernelGGL(topk_scan_kernel<4>, grid, dim3(kBlock), lds, stream, user_mat, item_tab, D, n_items, query_user,
-                               n, mask_ptr, mask_idx, k, chunk, nci, ws);
-    }
-    WR_LAUNCH_CHECK("topk_scan_kernel");
-    const dim3 mgrid((unsigned)((n + kBlock / 64 - 1) / (kBlock / 64)));
-    if (big)
-        hipLaunchKernelGGL(topk_merge_kernel<8>, mgrid, dim3(kBlock), 0, stream, ws, n, nci, k, out_item, out_score);
-    else
-        hipLaunchKernelGGL(topk_merge_kernel<4>, mgrid, dim3(kBlock), 0, stream, ws, n, nci, k, out_item, out_score);
-    WR_LAUNCH_CHECK("topk_merge_kernel");
-    return WR_OK;
+    return topk_launch(user_mat, item_tab, n_items, D, query_user, query_user, n, mask_ptr, mask_idx, k, out_item, out_score,
+                       workspace, reinterpret_cast<hipStream_t>(stream_));
+}
+
+int32_t wr_topk_recommend_rows(const float *query_mat, int64_t n_query_rows, const float *item_tab, int64_t n_items, int32_t D,
+                               const int64_t *query_row, int64_t n, const int64_t *mask_row, int64_t n_mask_rows,
+                               const int64_t *mask_ptr, const int32_t *mask_idx, int32_t k, int32_t *out_item,
+                               float *out_score, void *workspace, int64_t workspace_bytes, void *stream_) {
+    int32_t rc;
+    if ((rc = check_table(query_mat, n_query_rows, D, "query_mat")) != WR_OK) return rc;
+    if ((rc = check_table(item_tab, n_items, D, "item_tab")) != WR_OK) return rc;
+    WR_REQUIRE(out_item && out_score, WR_E_NULL, "topk_recommend_rows: NULL argument");
+    WR_REQUIRE((mask_ptr == nullptr) == (mask_idx == nullptr) && (mask_ptr == nullptr) == (mask_row == nullptr), WR_E_NULL,
+               "topk_recommend_rows: mask_row, mask_ptr and mask_idx go together");
+    WR_REQUIRE(mask_ptr == nullptr || n_mask_rows >= 1, WR_E_SHAPE, "topk_recommend_rows: n_mask_rows=%lld with a mask",
+               (long long)n_mask_rows);
+    if ((rc = topk_check("topk_recommend_rows", n, n_items, D, k, workspace, workspace_bytes)) != WR_OK) return rc;
+    WR_REQUIRE(query_row != nullptr || n <= n_query_rows, WR_E_SHAPE,
+               "topk_recommend_rows: n=%lld rows but query_mat has %lld and no query_row is given", (long long)n,
+               (long long)n_query_rows);
+    if (n == 0) return WR_OK;
+    return topk_launch(query_mat, item_tab, n_items, D, query_row, mask_row, n, mask_ptr, mask_idx, k, out_item, out_score,
+                       workspace, reinterpret_cast<hipStream_t>(stream_));
 }
 
 }  // extern "C"

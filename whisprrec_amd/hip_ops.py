@@ -1170,6 +1170,84 @@ def topk_recommend(user_mat, item_tab, users, k, mask_ptr=None, mask_idx=None):
     return items.to(torch.int64), scores
 
 
+def _rows_args(fn, query_mat, item_tab, n, mask_row, mask_ptr, mask_idx, query_row):
+    """the argument checks rank_eval_rows and topk_recommend_rows share -> (query_row, mask_row) as int64 or None"""
+    if (mask_ptr is None) != (mask_idx is None):
+        raise ValueError("mask_ptr and mask_idx go together")
+    if (mask_ptr is None) != (mask_row is None):
+        raise ValueError("%s: mask_row goes with mask_ptr and mask_idx (the row of the mask that each row uses)" % fn)
+    _req(query_mat, torch.float32, "query_mat", 2)
+    _req(item_tab, torch.float32, "item_tab", 2)
+    if item_tab.shape[1] != query_mat.shape[1]:
+        raise ValueError("query_mat and item_tab have different widths (%d, %d)" % (query_mat.shape[1], item_tab.shape[1]))
+    if mask_ptr is not None:
+        _req(mask_ptr, torch.int64, "mask_ptr", 1)
+        _req(mask_idx, torch.int32, "mask_idx", 1)
+        mask_row = _idx64(mask_row.reshape(-1), "mask_row")
+    if query_row is not None:
+        query_row = _idx64(query_row.reshape(-1), "query_row")
+        n = query_row.numel() if n is None else n
+        if query_row.numel() != n:
+            raise ValueError("%s: query_row has %d entries for %d rows" % (fn, query_row.numel(), n))
+    else:
+        n = query_mat.shape[0] if n is None else n
+        if n > query_mat.shape[0]:
+            raise ValueError("%s: %d rows but query_mat has %d and no query_row is given" % (fn, n, query_mat.shape[0]))
+    if mask_row is not None and mask_row.numel() != n:
+        raise ValueError("%s: mask_row has %d entries for %d rows" % (fn, mask_row.numel(), n))
+    return n, query_row, mask_row
+
+
+def rank_eval_rows(query_mat, item_tab, eval_target, mask_row=None, mask_ptr=None, mask_idx=None, query_row=None):
+    """rank_eval with one query vector per evaluation row (wr_rank_eval_rows; sequential models): row e scores with
+    query_mat[query_row[e]] (query_row None: query_mat[e]) and is masked by the list of row mask_row[e] of the CSR
+    mask_ptr / mask_idx — its user; several rows may share one.  Returns (rank int32 [n], target_score fp32 [n])."""
+    n, qr, mr = _rows_args("rank_eval_rows", query_mat, item_tab, eval_target.numel(), mask_row, mask_ptr, mask_idx, query_row)
+    et = _idx64(eval_target.reshape(-1), "eval_target")
+    rank = torch.empty(n, dtype=torch.int32, device=query_mat.device)
+    tsc = torch.empty(n, dtype=torch.float32, device=query_mat.device)
+    n_mask_rows = 0 if mask_ptr is None else mask_ptr.numel() - 1
+    abi.check(abi.lib().wr_rank_eval_rows(_p(query_mat), query_mat.shape[0], _p(item_tab), item_tab.shape[0], query_mat.shape[1],
+                                          _p(qr), _p(et), n, _p(mr), n_mask_rows, _p(mask_ptr), _p(mask_idx), _p(rank), _p(tsc),
+                                          _stream()),
+              "wr_rank_eval_rows")
+    return rank, tsc
+
+
+def topk_recommend_rows(query_mat, item_tab, k, mask_row=None, mask_ptr=None, mask_idx=None, query_row=None):
+    """topk_recommend with one query vector per row (wr_topk_recommend_rows; the roles as in rank_eval_rows): n =
+    len(query_row), or every row of query_mat.  Order, ties, padding and the bits of the scores are topk_recommend's.
+    Returns (items int64 [n, k], scores float32 [n, k]) on the device."""
+    n, qr, mr = _rows_args("topk_recommend_rows", query_mat, item_tab, None, mask_row, mask_ptr, mask_idx, query_row)
+    k, D = int(k), int(query_mat.shape[1])
+    if not topk_supports(D, k):
+        raise abi.WhisprRecHipError("topk_recommend_rows does not support D=%d, k=%d (1 <= k <= %d; D as for rank_eval)"
+                                    % (D, k, TOPK_MAX_K))
+    L, dev = abi.lib(), query_mat.device
+    n_items = item_tab.shape[0]
+    n_mask_rows = 0 if mask_ptr is None else mask_ptr.numel() - 1
+    items = torch.empty((n, k), dtype=torch.int32, device=dev)
+    scores = torch.empty((n, k), dtype=torch.float32, device=dev)
+    # rows in blocks whose workspace stays under the cap, as topk_recommend blocks its users
+    block = max(n, 1)
+    while block > 128 and abi.check_size(L.wr_topk_workspace_bytes(block, n_items, D, k), "wr_topk_workspace_bytes") \
+            > TOPK_WORKSPACE_CAP:
+        block = (block + 1) // 2
+    ws = workspace(dev, "topk")
+    for lo in range(0, n, block):
+        hi = min(n, lo + block)
+        nb = abi.check_size(L.wr_topk_workspace_bytes(hi - lo, n_items, D, k), "wr_topk_workspace_bytes")
+        buf = ws.get(nb)
+        # without query_row a block's queries are the rows lo.. of query_mat: the table pointer moves with the block
+        qmat, q_rows = (query_mat, query_mat.shape[0]) if qr is not None else (query_mat[lo:hi], hi - lo)
+        abi.check(L.wr_topk_recommend_rows(_p(qmat), q_rows, _p(item_tab), n_items, D, _p(qr[lo:hi]) if qr is not None else None,
+                                           hi - lo, _p(mr[lo:hi]) if mr is not None else None, n_mask_rows, _p(mask_ptr),
+                                           _p(mask_idx), k, _p(items[lo:hi]), _p(scores[lo:hi]), _p(buf), buf.numel(),
+                                           _stream()),
+                  "wr_topk_recommend_rows")
+    return items.to(torch.int64), scores
+
+
 # ----------------------------------------------------------------------------------------------- InfoNCE (SGL)
 _INFONCE_WS = {}        # (device, stream, n, B, D) -> (workspace bytes, error word): nothing is allocated after the first call
 

@@ -6,6 +6,8 @@ Same flow as the reference: pick model / reader / runner classes by name (main.p
 (:117-122), derive the log / checkpoint names (:125-133), seed (utils.init_seed), read the corpus, build the model, train
 with evaluation on dev every epoch, load the best checkpoint, report test metrics (:30-86).  The corpus pickle cache of
 the reference (:53-63) is not reproduced: the NumPy reader takes a fraction of a second.  Needs a GPU (there is no CPU path).
+With ``--runner_name HipRunner``: ``--save_rec K`` writes the K best items of every dev row (sequential models included, one
+query per row), ``--seq_eval_native 1`` evaluates sequential models on the device.
 """
 import argparse
 import logging

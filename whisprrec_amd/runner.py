@@ -286,14 +286,20 @@ def make_hip_runner(base_runner_cls):
             parser.add_argument("--save_rec", type=int, default=0,
                                 help="K > 0: after training, write the K best items of every dev row to "
                                      "<path>/<dataset>/rec-<model_name>.csv.")
+            parser.add_argument("--seq_eval_native", type=int, default=0, choices=[0, 1],
+                                help="1: evaluate sequential models (SASRec) on the device: queries in chunks, ranks from "
+                                     "wr_rank_eval_rows, no [n_eval, n_items] matrix; 0: the host loop.")
             return base_runner_cls.parse_runner_args(parser)
 
         def __init__(self, args):
             super().__init__(args)
             self.device_epoch_prep = int(getattr(args, "device_epoch_prep", 0))
             self.hip_graphs = int(getattr(args, "hip_graphs", 1))
+            self.seq_eval_native = bool(int(getattr(args, "seq_eval_native", 0)))
             self.seed = int(getattr(args, "random_seed", 3407))
             self._epoch_cache = None
+            self._hist_cache = {}           # id(dataset) -> (dataset, histories, lengths): train, dev and test alternate
+            self._seq_eval_warned = False
 
         def _device_epoch(self, dataset, dev, epoch, pipelined=False):
             """negatives (wr_sample_negatives) + shuffle, all on the device: no Python loop over rows"""
@@ -327,9 +333,13 @@ def make_hip_runner(base_runner_cls):
         def evaluate(self, dataset, topks, metrics):
             """Full-ranking evaluation on the device when the model exposes its factor matrices (``eval_factors``): ranks
             from wr_rank_eval (MFMA score tiles + on-the-fly masking + counting), no [n_eval, n_items] matrix, no Python
-            loop over rows (reference BaseRunner.py:218-258).  Otherwise the inherited host path."""
+            loop over rows (reference BaseRunner.py:218-258).  With --seq_eval_native 1 a sequential dataset whose model has
+            the query protocol (``eval_queries`` / ``eval_items``: SASRec) goes through ``rank_rows`` (wr_rank_eval_rows).
+            Otherwise the inherited host path."""
             model = dataset.model
             from . import hip_ops
+            if self._seq_eval_ok(dataset):
+                return self.metrics_from_ranks(self.rank_rows(dataset), topks, metrics)
             if not hasattr(model, "eval_factors") or not hip_ops.rank_eval_supports(model.eval_factors()[0].shape[1]):
                 return base_runner_cls.evaluate(self, dataset, topks, metrics)
             from . import hip_ops
@@ -342,6 +352,69 @@ def make_hip_runner(base_runner_cls):
             et = torch.from_numpy(np.ascontiguousarray(dataset.data["item_id"])).to(dev)
             rank, _ = hip_ops.rank_eval(user_mat.contiguous(), item_mat.contiguous(), eu, et, ptr, idx)
             return self.metrics_from_ranks(rank.cpu().numpy().astype(np.int64), topks, metrics)
+
+        @staticmethod
+        def _has_query_protocol(model):
+            return hasattr(model, "eval_queries") and hasattr(model, "eval_items")
+
+        def _seq_eval_ok(self, dataset):
+            """--seq_eval_native 1 and a sequential dataset whose model has the query protocol and an embedding size the
+            kernels take; anything else under the flag is logged once and evaluated as without it"""
+            if not self.seq_eval_native:
+                return False
+            from . import hip_ops
+            model = dataset.model
+            why = None
+            if "position" not in dataset.data:
+                why = "the dataset is not sequential"
+            elif not self._has_query_protocol(model) or not hasattr(model, "history_max"):
+                why = "%s has no eval_queries() / eval_items()" % type(model).__name__
+            elif not hip_ops.rank_eval_supports(model.eval_items().shape[1]):
+                why = "the evaluation kernels do not take embedding size %d" % model.eval_items().shape[1]
+            if why is None:
+                return True
+            if not self._seq_eval_warned:
+                logging.warning("--seq_eval_native 1: %s; keeping the evaluation path of --seq_eval_native 0", why)
+                self._seq_eval_warned = True
+            return False
+
+        def _row_queries(self, dataset, rows=None):
+            """[n, D] query vectors of the rows of a sequential dataset (`rows`: a subset, in that order), through the
+            model's eval_queries in chunks of eval_batch_size"""
+            model = dataset.model
+            dev = next(model.parameters()).device
+            hist, lens = self._history_columns(dataset, dev)
+            if rows is not None:
+                sel = torch.from_numpy(np.ascontiguousarray(rows)).to(dev)
+                hist, lens = hist[sel], lens[sel]
+            return self._queries_of(model, hist, lens)
+
+        def _queries_of(self, model, hist, lens):
+            n, step = hist.shape[0], max(int(self.eval_batch_size), 1)
+            out = torch.empty((n, model.eval_items().shape[1]), dtype=torch.float32, device=hist.device)
+            for lo in range(0, n, step):
+                out[lo:lo + step] = model.eval_queries(hist[lo:lo + step], lens[lo:lo + step])
+            return out
+
+        def rank_rows(self, dataset):
+            """Rank of every row's ground-truth item among all (unmasked) items, int64 [n_eval], for a sequential dataset
+            whose model has the query protocol: what BaseRunner.interface + evaluate_method compute for it (BaseRunner.py:
+            218-258) without the per-sample collate, the [n_eval, n_items] matrix, the Python masking loop and the argsort.
+            Histories by array work, queries in chunks of eval_batch_size, then one wr_rank_eval_rows call in which row e
+            scores with its own query and is masked by the lists of its user."""
+            from . import hip_ops
+            model = dataset.model
+            consume_loader_seed()                       # the evaluation DataLoader this replaces would draw its base seed
+            model.eval()
+            queries = self._row_queries(dataset)
+            dev = queries.device
+            ptr, idx = self._clicked_mask(dataset.corpus, bool(model.test_all), model.user_num, dev)
+            et = torch.from_numpy(np.ascontiguousarray(dataset.data["item_id"])).to(torch.int64).to(dev)
+            mrow = None
+            if ptr is not None:
+                mrow = torch.from_numpy(np.ascontiguousarray(dataset.data["user_id"])).to(torch.int64).to(dev)
+            rank, _ = hip_ops.rank_eval_rows(queries, model.eval_items().detach().contiguous(), et, mrow, ptr, idx)
+            return rank.cpu().numpy().astype(np.int64)
 
         def _clicked_mask(self, corpus, test_all, n_user_rows, dev):
             """device CSR of the items the full ranking sets to -inf (BaseRunner.py:246-255): each user's train + dev + test
@@ -367,9 +440,14 @@ def make_hip_runner(base_runner_cls):
               exclude="train":   only the training items (corpus.train_clicked_set);
               exclude="none":    every item.
             Needs a model whose scores are inner products of two factor matrices (``eval_factors``: BPRMF, LightGCN, SGL).
-            SASRec is out of scope: its query vector depends on each row's history, not on the user id alone."""
+            A sequential model (SASRec) has one query per row, made from that row's history and not from the user id alone:
+            use ``recommend_rows`` for rows of a dataset and ``recommend_next`` for histories given directly."""
             from . import hip_ops
             if not hasattr(model, "eval_factors"):
+                if self._has_query_protocol(model):
+                    raise NotImplementedError("%s scores with one query per row (eval_queries), not per user: use "
+                                              "HipRunner.recommend_rows(dataset, k) or recommend_next(model, corpus, "
+                                              "histories, k)" % type(model).__name__)
                 raise NotImplementedError("%s has no eval_factors(): HipRunner.recommend needs a model whose scores are "
                                           "inner products of a user and an item matrix" % type(model).__name__)
             model.eval()
@@ -379,29 +457,104 @@ def make_hip_runner(base_runner_cls):
                 raise NotImplementedError("%s: HipRunner.recommend does not support embedding size %d with k=%d"
                                           % (type(model).__name__, D, k))
             dev = user_mat.device
-            if exclude == "clicked":
-                ptr, idx = self._clicked_mask(corpus, True, user_mat.shape[0], dev)
-            elif exclude == "train":
-                cache = getattr(self, "_train_mask_cache", None)
-                if cache is None or cache[0] is not corpus:
-                    cache = self._train_mask_cache = (corpus,) + hip_ops.clicked_csr(corpus.train_clicked_set,
-                                                                                      user_mat.shape[0], dev)
-                ptr, idx = cache[1], cache[2]
-            elif exclude == "none":
-                ptr = idx = None
-            else:
-                raise ValueError("exclude must be 'clicked', 'train' or 'none' (got %r)" % (exclude,))
+            ptr, idx = self._exclude_mask(corpus, exclude, user_mat.shape[0], dev)
             uq = torch.from_numpy(np.ascontiguousarray(np.asarray(users, dtype=np.int64).reshape(-1))).to(dev)
             with torch.no_grad():
                 items, scores = hip_ops.topk_recommend(user_mat.contiguous(), item_mat.contiguous(), uq, k, ptr, idx)
             return items.cpu().numpy(), scores.cpu().numpy()
+
+        def _exclude_mask(self, corpus, exclude, n_user_rows, dev):
+            """the mask CSR behind `exclude` of recommend / recommend_rows / recommend_next, from the runner's caches"""
+            from . import hip_ops
+            if exclude == "clicked":
+                return self._clicked_mask(corpus, True, n_user_rows, dev)
+            if exclude == "train":
+                cache = getattr(self, "_train_mask_cache", None)
+                if cache is None or cache[0] is not corpus:
+                    cache = self._train_mask_cache = (corpus,) + hip_ops.clicked_csr(corpus.train_clicked_set, n_user_rows, dev)
+                return cache[1], cache[2]
+            if exclude == "none":
+                return None, None
+            raise ValueError("exclude must be 'clicked', 'train' or 'none' (got %r)" % (exclude,))
+
+        def _topk_rows(self, model, corpus, queries, users, k, exclude):
+            """top-K of one query per row, masked by the lists of `users` (None: no mask) -> numpy (items, scores)"""
+            from . import hip_ops
+            dev = queries.device
+            ptr, idx = self._exclude_mask(corpus, exclude if users is not None else "none", model.user_num, dev)
+            mrow = None
+            if ptr is not None:
+                mrow = torch.from_numpy(np.ascontiguousarray(np.asarray(users, dtype=np.int64).reshape(-1))).to(dev)
+            items, scores = hip_ops.topk_recommend_rows(queries, model.eval_items().detach().contiguous(), k, mrow, ptr, idx)
+            return items.cpu().numpy(), scores.cpu().numpy()
+
+        def _check_query_model(self, model, k, what):
+            from . import hip_ops
+            if not self._has_query_protocol(model) or not hasattr(model, "history_max"):
+                raise NotImplementedError("%s has no eval_queries() / eval_items(): HipRunner.%s needs a sequential model "
+                                          "with the query protocol" % (type(model).__name__, what))
+            D = model.eval_items().shape[1]
+            if not hip_ops.topk_supports(D, k):
+                raise NotImplementedError("%s: HipRunner.%s does not support embedding size %d with k=%d"
+                                          % (type(model).__name__, what, D, k))
+
+        def recommend_rows(self, dataset, k, rows=None, exclude="clicked"):
+            """The k best items for rows of a sequential dataset (all of them, or the row numbers `rows` in that order): every
+            row scores with the query of its own history (``eval_queries``) and is masked by its user's lists
+            (wr_topk_recommend_rows).  `exclude`, order, ties and padding as in ``recommend``.  Returns numpy (items int64
+            [n, k], scores float32 [n, k])."""
+            model = dataset.model
+            if "position" not in dataset.data:
+                raise NotImplementedError("recommend_rows needs a sequential dataset (rows with a position); use recommend")
+            self._check_query_model(model, k, "recommend_rows")
+            users = np.asarray(dataset.data["user_id"], dtype=np.int64)
+            if rows is not None:
+                rows = np.asarray(rows, dtype=np.int64).reshape(-1)
+                if rows.size and (rows.min() < 0 or rows.max() >= len(users)):
+                    raise IndexError("recommend_rows: row number out of range")
+                users = users[rows]
+            model.eval()
+            return self._topk_rows(model, dataset.corpus, self._row_queries(dataset, rows), users, k, exclude)
+
+        def recommend_next(self, model, corpus, histories, k, users=None, exclude="clicked"):
+            """The k best next items after each of `histories` (item-id sequences, oldest first; the last history_max items
+            count) — histories that need not be in any dataset.  users: the user id behind each history, whose lists
+            `exclude` hides; without users nothing is masked.  Returns numpy (items int64 [n, k], scores float32 [n, k])."""
+            self._check_query_model(model, k, "recommend_next")
+            T = int(model.history_max)
+            seqs = [np.asarray(h, dtype=np.int64).reshape(-1) for h in histories]
+            seqs = [h[-T:] if T > 0 else h for h in seqs]
+            if any(h.size == 0 for h in seqs):
+                raise ValueError("recommend_next: an empty history has no query")
+            if users is not None:
+                users = np.asarray(users, dtype=np.int64).reshape(-1)
+                if users.size != len(seqs):
+                    raise ValueError("recommend_next: %d users for %d histories" % (users.size, len(seqs)))
+                if users.size and (users.min() < 0 or users.max() >= model.user_num):
+                    raise IndexError("recommend_next: user id out of range")
+            dev = next(model.parameters()).device
+            if not seqs:
+                return np.zeros((0, k), np.int64), np.zeros((0, k), np.float32)
+            lens = np.asarray([h.size for h in seqs], dtype=np.int64)
+            hist = np.zeros((len(seqs), int(lens.max())), np.int64)
+            for r, h in enumerate(seqs):
+                hist[r, :h.size] = h
+            if hist.min() < 0 or hist.max() >= model.item_num:
+                raise IndexError("recommend_next: item id out of range")
+            model.eval()
+            queries = self._queries_of(model, torch.from_numpy(hist).to(dev), torch.from_numpy(lens).to(dev))
+            return self._topk_rows(model, corpus, queries, users, k, exclude)
 
         def save_rec_results(self, dataset, k, path, sep="\t"):
             """The reference's save_rec_results (src/main.py:83-102, commented out there): one line per row of `dataset`, in
             order, with that row's user and its k best items, masked as `evaluate` masks them for this model (test_all)."""
             model = dataset.model
             users = np.asarray(dataset.data["user_id"], dtype=np.int64)
-            items, _ = self.recommend(model, dataset.corpus, users, k, exclude="clicked" if model.test_all else "none")
+            exclude = "clicked" if model.test_all else "none"
+            if "position" in dataset.data and self._has_query_protocol(model):      # one query per row, not per user
+                items, _ = self.recommend_rows(dataset, k, exclude=exclude)
+            else:
+                items, _ = self.recommend(model, dataset.corpus, users, k, exclude=exclude)
             write_rec_csv(path, users, items, sep)
             return path
 
@@ -482,9 +635,10 @@ def make_hip_runner(base_runner_cls):
 
         def _history_columns(self, dataset, dev):
             """[n, history_max] item histories (left-aligned, zero-padded like collate_batch's pad_sequence) and their lengths
-            for every training row of a sequential dataset, built once with array operations: row i takes the last
-            history_max entries of its user's history before position[i] (SequentialModel.Dataset._get_feed_dict)."""
-            cached = getattr(self, "_hist_cache", None)
+            for every row of a sequential dataset, built once per dataset object with array operations (training and
+            evaluation alternate every epoch: train, dev and test each keep their own): row i takes the last history_max
+            entries of its user's history before position[i] (SequentialModel.Dataset._get_feed_dict)."""
+            cached = self._hist_cache.get(id(dataset))
             if cached is not None and cached[0] is dataset:
                 return cached[1], cached[2]
             T = int(dataset.model.history_max)
@@ -503,7 +657,7 @@ def make_hip_runner(base_runner_cls):
             valid = np.arange(width)[None, :] < length[:, None]
             hist = np.where(valid, flat[np.minimum(idx, flat.size - 1)], 0)
             out = (torch.from_numpy(hist).to(dev), torch.from_numpy(length).to(dev))
-            self._hist_cache = (dataset, out[0], out[1])
+            self._hist_cache[id(dataset)] = (dataset, out[0], out[1])     # holds the dataset: its id cannot be reused
             return out
 
         def fit(self, dataset, epoch=-1):

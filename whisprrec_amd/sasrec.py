@@ -172,6 +172,23 @@ def make_sasrec(sequential_model_cls):
         def full_predict(self, feed_dict):
             return torch.matmul(self.forward(feed_dict), self.item_embedding.weight.t())
 
+        # The query protocol of HipRunner's device evaluation (--seq_eval_native 1) and recommend_rows: a model whose score
+        # of row e against item j is <eval_queries(...)[e], eval_items()[j]>.
+        def eval_queries(self, history_items, lengths):
+            """[n, D] query vectors of rows with these histories ([n, T] left-aligned, zero-padded) and lengths: `forward` in
+            eval mode without autograd, on the block path `forward` itself picks.  The training flag is restored."""
+            was_training = self.training
+            self.eval()
+            try:
+                with torch.no_grad():
+                    return self.forward({"history_items": history_items, "lengths": lengths})
+            finally:
+                self.train(was_training)
+
+        def eval_items(self):
+            """[n_items, D] item side of the scores: full_predict's second operand"""
+            return self.item_embedding.weight
+
     SASRec.__qualname__ = "SASRec"
     return SASRec
 
