@@ -859,6 +859,57 @@ int32_t wr_sasblock_fwd(const float *x, int64_t B, int32_t T, int32_t D, int32_t
 int32_t wr_sasblock_bwd(const float *x, const float *grad_out, int64_t B, int32_t T, int32_t D, int32_t d_ff, int32_t n_heads,
                         const float *const *params, float p, uint64_t seed, int32_t training, const float *gmax, float *gx,
                         float *gparams, void *workspace, int64_t workspace_bytes, void *stream);
+/* K13 with a key-length mask instead of the causal one (ContraRec's BERT4RecEncoder, src/models/sequential/ContraRec.py:216-233:
+ * attn_mask = valid_mask.view(B, 1, 1, T)).  The arguments of wr_sasblock_fwd / _bwd plus key_len (int64 [B] on the device) and
+ * err_word (may be NULL; the caller clears it).  The score of query i against key j is kept iff j < key_len[b], for EVERY query
+ * i in 0..T-1: padded query positions are ordinary queries.  Everything else is the K13 contract unchanged — the call-wide
+ * maximum over the kept scores, the zeroed-row rule, the dropout sites, no float atomics, fixed fold orders, same bits from run to
+ * run, no allocation, no host round trip, the supported shapes, argument errors refused before any launch.
+ *   - A key_len outside [1, T] is clamped into it before it bounds any loop, and err_word[0] |= 1.
+ *   - The causal entry points are the same templates with the loop bound j <= i: their results are unchanged. */
+int32_t wr_sasblock_fwd_keys(const float *x, int64_t B, int32_t T, int32_t D, int32_t d_ff, int32_t n_heads,
+                             const float *const *params, float p, uint64_t seed, int32_t training, float *out, float *gmax,
+                             void *workspace, int64_t workspace_bytes, void *stream, const int64_t *key_len, int32_t *err_word);
+int32_t wr_sasblock_bwd_keys(const float *x, const float *grad_out, int64_t B, int32_t T, int32_t D, int32_t d_ff,
+                             int32_t n_heads, const float *const *params, float p, uint64_t seed, int32_t training,
+                             const float *gmax, float *gx, float *gparams, void *workspace, int64_t workspace_bytes, void *stream,
+                             const int64_t *key_len, int32_t *err_word);
+
+/* ---------------------------------------------------------------------------------------------------
+ * K15  Supervised contrastive loss of ContraRec (ContraLoss, src/models/sequential/ContraRec.py:141-204) and its gradient,
+ *      without any [2B, 2B] array.  F is [2B, D] fp32 row-major, raw and unnormalised: rows 0..B-1 are view a, rows B..2B-1
+ *      view b; labels int64 [B], row r has label labels[r mod B].  With N = 2B and z_i = F_i / max(|F_i|, 1e-12):
+ *   s_ij = <z_i, z_j> / tau        m_i = max_j s_ij (diagonal included)        l_ij = s_ij - 2 m_i   (the reference subtracts the
+ *   E_i  = sum_{j != i} exp(l_ij)                                                                    row maximum twice, :181-182)
+ *   P_i  = { j != i : label_j == label_i }        c_i = |P_i| + 1e-10
+ *   loss = weight * (1/N) * sum_i (-tau / c_i) * sum_{j in P_i} ( l_ij - log(E_i + 1e-10) )
+ *   gF   = d loss / d F with m_i held constant:  G_ij = (-tau/N) ( [j in P_i] / c_i - (|P_i| / c_i) exp(l_ij) / (E_i + 1e-10) )
+ *          for j != i, 0 on the diagonal;  gz = weight (G + G^T) z / tau;  gF_i = (gz_i - <gz_i, z_i> z_i) / |F_i|
+ *          (a row with |F_i| < 1e-12 follows K12's eps rule: gF_i = gz_i / 1e-12)
+ *   - loss [1] on the device: loss_out = (accumulate ? loss_in : 0) + this loss.  gF [2B, D] is fully written; NULL = loss
+ *     only, and that loss has the bits of the full call's.
+ *   - Scores: the fp32 k-ordered chain of v_mfma_f32_32x32x2_f32 from wr_score_tiles.h with the normalised rows as both
+ *     operands, so s_ij and s_ji have the same bits.  Pass 1 leaves m_i, sum_{j != i} exp(s_ij - 1/tau), |P_i| and
+ *     sum_{j in P_i} s_ij per row; pass 2 rebuilds each tile, forms G_ij + G_ji from the statistics of its row and its column
+ *     and multiplies by z on the same instruction.
+ *   - tau domain: finite tau > 0 is accepted; parity is claimed for tau >= 0.05.  Cosines are bounded, so the exponentials
+ *     are taken as e_ij = exp(s_ij - 1/tau) in (0, ~1]; with r_i = exp(1/tau - 2 m_i), exp(l_ij) = e_ij r_i and the 1e-10 joins
+ *     the row's sum as 1e-10 / r_i ~ 1e-10 e^{1/tau}.  Below that domain: the reference's own exp(l_ij) ~ exp(-3/tau) of a
+ *     dissimilar pair leaves the normal fp32 range under tau ~ 0.034 and e_ij under tau ~ 0.023 (such terms count as 0, the loss
+ *     tends to (-tau / c_i) sum_P (l_ij - log 1e-10), here as there); under tau ~ 0.009 1e-10 / r_i overflows and the loss is inf.
+ *   - Determinism: no float atomics; column chunks go to partials folded in chunk order, the N row terms in a fixed
+ *     order.  Same inputs, same bits.
+ *   - D in {32, 64, 128} (wr_supcon_supported), 1 <= B, 2B <= 2^15; anything else, a NULL or misaligned (16 B) pointer or a
+ *     short workspace is refused before any launch.  err_word is reserved (labels are compared, never used as indices: no
+ *     value is out of range); it may be NULL and is not written.
+ *   - workspace >= wr_supcon_workspace_bytes(B, D), 16-byte aligned: the normalised rows, per-row statistics and a bounded
+ *     number of [row, D] chunk partials — never N x N.
+ *   - No host round trip, no allocation: capturable into a hipGraph. */
+int32_t wr_supcon_supported(int32_t D);
+int64_t wr_supcon_workspace_bytes(int64_t B, int32_t D);
+int32_t wr_supcon_loss_grad(const float *F, int64_t B, int32_t D, const int64_t *labels, float tau, float *loss,
+                            int32_t accumulate, float weight, float *gF, int32_t *err_word, void *workspace,
+                            int64_t workspace_bytes, void *stream);
 
 /* LightGCN.predict's per-batch tail in two launches (src/models/general/LightGCN.py:156-175, src/utils/loss.py:37-39,94-98):
  *   loss[0] = mean_b( -log(1e-10 + sigmoid(<Ua[u_b], Ia[p_b]> - <Ua[u_b], Ia[n_b]>)) )

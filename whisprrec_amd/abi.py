@@ -187,6 +187,13 @@ SIGNATURES = {
                                 c_vp]),
     "wr_sasblock_bwd": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp, c_f32, ctypes.c_uint64, c_i32, c_vp, c_vp, c_vp,
                                 c_vp, c_i64, c_vp]),
+    "wr_sasblock_fwd_keys": (c_i32, [c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp, c_f32, ctypes.c_uint64, c_i32, c_vp, c_vp, c_vp,
+                                     c_i64, c_vp, c_vp, c_vp]),
+    "wr_sasblock_bwd_keys": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp, c_f32, ctypes.c_uint64, c_i32, c_vp, c_vp,
+                                     c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
+    "wr_supcon_supported": (c_i32, [c_i32]),
+    "wr_supcon_workspace_bytes": (c_i64, [c_i64, c_i32]),
+    "wr_supcon_loss_grad": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_f32, c_vp, c_i32, c_f32, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "wr_lightgcn_loss_workspace_bytes": (c_i64, [c_i64]),
     "wr_lightgcn_loss": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_vp, c_vp, c_vp, c_i64, c_f32, c_vp, c_vp, c_vp,
                                  c_i64, c_vp]),

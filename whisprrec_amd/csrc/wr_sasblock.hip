@@ -27,6 +27,11 @@
 // autograd produces NaN gradients for such a row.  That regime is outside the parity claim.
 //
 // No float atomics, every sum has a fixed order: same inputs and seed, same bits.  No allocation, no host round trip.
+//
+// Two masks, one code: the kernels are templates over CAUSAL.  CAUSAL (SASRec, wr_sasblock_fwd / _bwd): query i keeps keys
+// j <= i.  !CAUSAL (ContraRec's BERT4RecEncoder, wr_sasblock_fwd_keys / _bwd_keys): every query i in 0..T-1 — the padded
+// positions are ordinary queries — keeps keys j < key_len[b]; a key_len outside [1, T] is clamped before it bounds any loop and
+// reported in err_word.  The mask is only the bound of the key loops (jend), workgroup-uniform in the second mode.
 #include "wr_common.h"
 
 namespace wr {
@@ -191,24 +196,25 @@ __device__ __forceinline__ void sas_ln_row_bwd(float *g, const float *xh, const 
     for (int c = 0; c < D; ++c) g[c] = rstd * (g[c] * gamma[c] - a - xh[c] * b);
 }
 
-// largest causal score of the sequence in sQ / sK over this thread's row (h, i), or -inf for a thread without a row
-template <int D>
-__device__ __forceinline__ float sas_row_max(const float *sQ, const float *sK, int T, int H, int dk, float sqrt_dk) {
+// largest kept score of the sequence in sQ / sK over this thread's row (h, i), or -inf for a thread without a row
+template <int D, bool CAUSAL>
+__device__ __forceinline__ float sas_row_max(const float *sQ, const float *sK, int T, int H, int dk, float sqrt_dk, int len) {
     constexpr int LD = D + 1;
     float m = -INFINITY;
     const int r = threadIdx.x;
     if (r < H * T) {
         const int h = r / T, i = r % T;
         const float *q = sQ + i * LD + h * dk;
-        for (int j = 0; j <= i; ++j) m = fmaxf(m, sas_dot(q, sK + j * LD + h * dk, dk) / sqrt_dk);
+        const int jend = CAUSAL ? i + 1 : len;
+        for (int j = 0; j < jend; ++j) m = fmaxf(m, sas_dot(q, sK + j * LD + h * dk, dk) / sqrt_dk);
     }
     return m;
 }
 
 // attention of one sequence: thread r = (h, i) owns one score row.  sA[i][h dk ..] = sum_j P_ij v_j, sZ[r] = sum_j exp
-template <int D>
+template <int D, bool CAUSAL>
 __device__ __forceinline__ void sas_attn_fwd(const float *sQ, const float *sK, const float *sV, float *sA, float *sZ, int T, int H,
-                                             int dk, float sqrt_dk, float gmax) {
+                                             int dk, float sqrt_dk, float gmax, int len) {
     constexpr int LD = D + 1;
     const int r = threadIdx.x;
     if (r >= H * T) return;
@@ -217,7 +223,8 @@ __device__ __forceinline__ void sas_attn_fwd(const float *sQ, const float *sK, c
     float *a = sA + i * LD + h * dk;
     for (int c = 0; c < dk; ++c) a[c] = 0.f;
     float Z = 0.f;
-    for (int j = 0; j <= i; ++j) {
+    const int jend = CAUSAL ? i + 1 : len;
+    for (int j = 0; j < jend; ++j) {
         const float e = expf(sas_dot(q, sK + j * LD + h * dk, dk) / sqrt_dk - gmax);
         Z += e;
         const float *v = sV + j * LD + h * dk;
@@ -227,10 +234,21 @@ __device__ __forceinline__ void sas_attn_fwd(const float *sQ, const float *sK, c
     sZ[r] = Z;
 }
 
+// key_len[b] clamped into [1, T]; a value outside is reported once per sequence (integer OR: order-free).  Causal: T, unused.
+template <bool CAUSAL>
+__device__ __forceinline__ int sas_key_len(const int64_t *__restrict__ key_len, int64_t b, int T, int32_t *__restrict__ err_word) {
+    if constexpr (CAUSAL) return T;
+    const int64_t l = key_len[b];
+    const bool bad = l < 1 || l > (int64_t)T;
+    if (bad && err_word != nullptr && threadIdx.x == 0) atomicOr(err_word, 1);
+    return bad ? (l < 1 ? 1 : T) : (int)l;
+}
+
 // ------------------------------------------------------------------------------------------------ forward, launch 1
-template <int D, int TM>
+template <int D, int TM, bool CAUSAL>
 __global__ __launch_bounds__(kBlock, TM <= 24 ? 2 : 1) void sas_fwd_pre_kernel(const float *__restrict__ x, int64_t B, int T, int H, SasParams P,
-                                                             float sqrt_dk, float *__restrict__ qkv, float *__restrict__ wgmax) {
+                                                             float sqrt_dk, float *__restrict__ qkv, float *__restrict__ wgmax,
+                                                             const int64_t *__restrict__ key_len, int32_t *__restrict__ err_word) {
     constexpr int LD = D + 1;
     __shared__ float sX[TM * LD], sQ[TM * LD], sK[TM * LD], sW[D * LD], red[4];
     const int dk = D / H;
@@ -251,18 +269,18 @@ __global__ __launch_bounds__(kBlock, TM <= 24 ? 2 : 1) void sas_fwd_pre_kernel(c
             });
             __syncthreads();
         }
-        m = fmaxf(m, sas_row_max<D>(sQ, sK, T, H, dk, sqrt_dk));
+        m = fmaxf(m, sas_row_max<D, CAUSAL>(sQ, sK, T, H, dk, sqrt_dk, sas_key_len<CAUSAL>(key_len, b, T, err_word)));
     }
     m = sas_block_max(m, red);
     if (threadIdx.x == 0) wgmax[blockIdx.x] = m;
 }
 
 // ------------------------------------------------------------------------------------------------ forward, launch 2
-template <int D, int TM>
+template <int D, int TM, bool CAUSAL>
 __global__ __launch_bounds__(kBlock, TM <= 24 ? 2 : 1) void sas_fwd_main_kernel(const float *__restrict__ x, int64_t B, int T, int H, SasParams P,
                                                               float sqrt_dk, SasDrop dr, const float *__restrict__ qkv,
                                                               const float *__restrict__ wgmax, int n_max, float *__restrict__ out,
-                                                              float *__restrict__ gmax_out) {
+                                                              float *__restrict__ gmax_out, const int64_t *__restrict__ key_len) {
     constexpr int LD = D + 1;
     __shared__ float sQ[TM * LD], sK[TM * LD], sV[TM * LD], sA[TM * LD], sW[D * LD], sZ[kBlock], red[4];
     const int dk = D / H;
@@ -277,7 +295,7 @@ __global__ __launch_bounds__(kBlock, TM <= 24 ? 2 : 1) void sas_fwd_main_kernel(
         sas_load<D>(src + T * D, sK, T);
         sas_load<D>(src + 2 * T * D, sV, T);
         __syncthreads();
-        sas_attn_fwd<D>(sQ, sK, sV, sA, sZ, T, H, dk, sqrt_dk, gmax);
+        sas_attn_fwd<D, CAUSAL>(sQ, sK, sV, sA, sZ, T, H, dk, sqrt_dk, gmax, sas_key_len<CAUSAL>(key_len, b, T, nullptr));
         __syncthreads();
         const float *xb = x + b * T * D;
         for (int e = threadIdx.x; e < T * D; e += kBlock) {
@@ -304,11 +322,12 @@ __global__ __launch_bounds__(kBlock, TM <= 24 ? 2 : 1) void sas_fwd_main_kernel(
 }
 
 // ------------------------------------------------------------------------------------------------ backward, launch 1
-template <int D, int TM>
+template <int D, int TM, bool CAUSAL>
 __global__ __launch_bounds__(kBlock, TM <= 24 ? 2 : 1) void sas_bwd_kernel(const float *__restrict__ x, const float *__restrict__ gout, int64_t B, int T,
                                                          int H, SasParams P, float sqrt_dk, SasDrop dr,
                                                          const float *__restrict__ gmax_p, float *__restrict__ gx,
-                                                         float *__restrict__ part) {
+                                                         float *__restrict__ part, const int64_t *__restrict__ key_len,
+                                                         int32_t *__restrict__ err_word) {
     constexpr int LD = D + 1, SLOT = TM * LD, ESLOT = (TM > D ? TM : D) * LD, NJ = D * D / kBlock;
     // slot:  s0 q   s1 k   s2 v   s3 xhat1 (A and y1 on the way; x again at the end)   s4 C, then dv   s5 H, then dk
     //        s6 y2 -> xhat2 -> d pre-activation -> dq   s7 x, then the gradient flowing back   s8 W^T staging, dO2, dA
@@ -325,6 +344,7 @@ __global__ __launch_bounds__(kBlock, TM <= 24 ? 2 : 1) void sas_bwd_kernel(const
     for (int64_t b = blockIdx.x; b < B; b += gridDim.x) {
         const float *xb = x + b * T * D;
         const uint64_t e0 = (uint64_t)(b * T * D);
+        const int len = sas_key_len<CAUSAL>(key_len, b, T, err_word);
         __syncthreads();
         // ---- the forward of this sequence again
         sas_load<D>(xb, s7, T);
@@ -336,7 +356,7 @@ __global__ __launch_bounds__(kBlock, TM <= 24 ? 2 : 1) void sas_bwd_kernel(const
             sas_mm<D, TM>(s7, s8, LD, T, [&](int t, int c, float v) { s[t * LD + c] = v + bias[c]; });
             __syncthreads();
         }
-        sas_attn_fwd<D>(s0, s1, s2, s3, sZ, T, H, dk, sqrt_dk, gmax);
+        sas_attn_fwd<D, CAUSAL>(s0, s1, s2, s3, sZ, T, H, dk, sqrt_dk, gmax, len);
         __syncthreads();
         for (int e = tid; e < T * D; e += kBlock) {
             const int o = (e / D) * LD + (e % D);
@@ -401,12 +421,13 @@ __global__ __launch_bounds__(kBlock, TM <= 24 ? 2 : 1) void sas_bwd_kernel(const
             float *dq = s6 + i * LD + ho;
             for (int c = 0; c < dk; ++c) dq[c] = 0.f;
             float delta = 0.f;
+            const int jend = CAUSAL ? i + 1 : len;
             if (Z > 0.f) {                                                  // a zeroed row passes nothing through its scores
-                for (int j = 0; j <= i; ++j) {
+                for (int j = 0; j < jend; ++j) {
                     const float p = expf(sas_dot(q, s1 + j * LD + ho, dk) / sqrt_dk - gmax) / Z;
                     delta = fmaf(p, sas_dot(da, s2 + j * LD + ho, dk), delta);
                 }
-                for (int j = 0; j <= i; ++j) {
+                for (int j = 0; j < jend; ++j) {
                     const float *kj = s1 + j * LD + ho;
                     const float p = expf(sas_dot(q, kj, dk) / sqrt_dk - gmax) / Z;
                     const float ds = p * (sas_dot(da, s2 + j * LD + ho, dk) - delta) / sqrt_dk;
@@ -422,7 +443,7 @@ __global__ __launch_bounds__(kBlock, TM <= 24 ? 2 : 1) void sas_bwd_kernel(const
             const float *kj = s1 + j * LD + ho, *vj = s2 + j * LD + ho;
             float *dkj = s5 + j * LD + ho, *dvj = s4 + j * LD + ho;
             for (int c = 0; c < dk; ++c) dkj[c] = dvj[c] = 0.f;
-            for (int i = j; i < T; ++i) {
+            for (int i = CAUSAL ? j : (j < len ? 0 : T); i < T; ++i) {     // the queries that keep key j
                 const float Z = sZ[h * T + i];
                 if (!(Z > 0.f)) continue;
                 const float *q = s0 + i * LD + ho, *da = s8 + i * LD + ho;
@@ -534,6 +555,72 @@ static int32_t sas_drop_of(const char *entry, float p, uint64_t seed, int32_t tr
 
 using namespace wr;
 
+template <bool CAUSAL>
+static int32_t sas_fwd(const char *entry, const float *x, int64_t B, int32_t T, int32_t D, int32_t d_ff, int32_t n_heads,
+                       const float *const *params, float p, uint64_t seed, int32_t training, const int64_t *key_len,
+                       int32_t *err_word, float *out, float *gmax, void *workspace, int64_t workspace_bytes, void *stream_) {
+    int32_t rc = sas_check(entry, B, T, D, d_ff, n_heads);
+    if (rc != WR_OK) return rc;
+    WR_REQUIRE(x && out && gmax && (CAUSAL || key_len), WR_E_NULL, "%s: NULL argument", entry);
+    WR_REQUIRE(aligned16(x) && aligned16(out), WR_E_ALIGN, "%s: x and out must be 16-byte aligned", entry);
+    SasParams P;
+    if ((rc = sas_check_params(entry, params, P)) != WR_OK) return rc;
+    SasDrop dr;
+    if ((rc = sas_drop_of(entry, p, seed, training, dr)) != WR_OK) return rc;
+    SasLayout L;
+    sas_layout(B, T, D, L);
+    if ((rc = check_workspace(entry, workspace, workspace_bytes, L.total)) != WR_OK) return rc;
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    char *ws = reinterpret_cast<char *>(workspace);
+    float *wgmax = reinterpret_cast<float *>(ws + L.wgmax), *qkv = reinterpret_cast<float *>(ws + L.qkv);
+    const int n_max = (int)(B < kSasFwdWg ? B : kSasFwdWg);
+    const float sqrt_dk = sqrtf((float)(D / n_heads));
+#define WR_SAS_FWD(D_, TM_)                                                                                                   \
+    do {                                                                                                                      \
+        hipLaunchKernelGGL((sas_fwd_pre_kernel<D_, TM_, CAUSAL>), dim3(n_max), dim3(kBlock), 0, stream, x, B, T, n_heads, P, sqrt_dk, \
+                           qkv, wgmax, key_len, err_word);                                                                    \
+        WR_LAUNCH_CHECK("sas_fwd_pre_kernel");                                                                                \
+        hipLaunchKernelGGL((sas_fwd_main_kernel<D_, TM_, CAUSAL>), dim3((unsigned)B), dim3(kBlock), 0, stream, x, B, T, n_heads, P, \
+                           sqrt_dk, dr, qkv, wgmax, n_max, out, gmax, key_len);                                               \
+        WR_LAUNCH_CHECK("sas_fwd_main_kernel");                                                                               \
+    } while (0)
+    WR_SAS_DISPATCH(D, T, WR_SAS_FWD);
+#undef WR_SAS_FWD
+    return WR_OK;
+}
+
+template <bool CAUSAL>
+static int32_t sas_bwd(const char *entry, const float *x, const float *grad_out, int64_t B, int32_t T, int32_t D, int32_t d_ff,
+                       int32_t n_heads, const float *const *params, float p, uint64_t seed, int32_t training,
+                       const int64_t *key_len, int32_t *err_word, const float *gmax, float *gx, float *gparams, void *workspace,
+                       int64_t workspace_bytes, void *stream_) {
+    int32_t rc = sas_check(entry, B, T, D, d_ff, n_heads);
+    if (rc != WR_OK) return rc;
+    WR_REQUIRE(x && grad_out && gmax && gx && gparams && (CAUSAL || key_len), WR_E_NULL, "%s: NULL argument", entry);
+    WR_REQUIRE(aligned16(x) && aligned16(grad_out) && aligned16(gx) && aligned16(gparams), WR_E_ALIGN,
+               "%s: x, grad_out, gx and gparams must be 16-byte aligned", entry);
+    SasParams P;
+    if ((rc = sas_check_params(entry, params, P)) != WR_OK) return rc;
+    SasDrop dr;
+    if ((rc = sas_drop_of(entry, p, seed, training, dr)) != WR_OK) return rc;
+    SasLayout L;
+    sas_layout(B, T, D, L);
+    if ((rc = check_workspace(entry, workspace, workspace_bytes, L.total)) != WR_OK) return rc;
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    float *part = reinterpret_cast<float *>(reinterpret_cast<char *>(workspace) + L.part);
+    const int n_wg = (int)(B < kSasBwdWg ? B : kSasBwdWg), n_par = 5 * D * D + 9 * D;
+    const float sqrt_dk = sqrtf((float)(D / n_heads));
+#define WR_SAS_BWD(D_, TM_)                                                                                                    \
+    hipLaunchKernelGGL((sas_bwd_kernel<D_, TM_, CAUSAL>), dim3(n_wg), dim3(kBlock), 0, stream, x, grad_out, B, T, n_heads, P, sqrt_dk, \
+                       dr, gmax, gx, part, key_len, err_word)
+    WR_SAS_DISPATCH(D, T, WR_SAS_BWD);
+#undef WR_SAS_BWD
+    WR_LAUNCH_CHECK("sas_bwd_kernel");
+    hipLaunchKernelGGL(sas_fold_kernel, dim3((n_par + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, part, n_wg, n_par, gparams);
+    WR_LAUNCH_CHECK("sas_fold_kernel");
+    return WR_OK;
+}
+
 extern "C" {
 
 int32_t wr_sasblock_supported(int32_t D, int32_t d_ff, int32_t n_heads, int32_t T) {
@@ -552,65 +639,31 @@ int64_t wr_sasblock_workspace_bytes(int64_t B, int32_t T, int32_t D, int32_t d_f
 
 int32_t wr_sasblock_fwd(const float *x, int64_t B, int32_t T, int32_t D, int32_t d_ff, int32_t n_heads, const float *const *params,
                         float p, uint64_t seed, int32_t training, float *out, float *gmax, void *workspace, int64_t workspace_bytes,
-                        void *stream_) {
-    int32_t rc = sas_check("wr_sasblock_fwd", B, T, D, d_ff, n_heads);
-    if (rc != WR_OK) return rc;
-    WR_REQUIRE(x && out && gmax, WR_E_NULL, "wr_sasblock_fwd: NULL argument");
-    WR_REQUIRE(aligned16(x) && aligned16(out), WR_E_ALIGN, "wr_sasblock_fwd: x and out must be 16-byte aligned");
-    SasParams P;
-    if ((rc = sas_check_params("wr_sasblock_fwd", params, P)) != WR_OK) return rc;
-    SasDrop dr;
-    if ((rc = sas_drop_of("wr_sasblock_fwd", p, seed, training, dr)) != WR_OK) return rc;
-    SasLayout L;
-    sas_layout(B, T, D, L);
-    if ((rc = check_workspace("wr_sasblock_fwd", workspace, workspace_bytes, L.total)) != WR_OK) return rc;
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    char *ws = reinterpret_cast<char *>(workspace);
-    float *wgmax = reinterpret_cast<float *>(ws + L.wgmax), *qkv = reinterpret_cast<float *>(ws + L.qkv);
-    const int n_max = (int)(B < kSasFwdWg ? B : kSasFwdWg);
-    const float sqrt_dk = sqrtf((float)(D / n_heads));
-#define WR_SAS_FWD(D_, TM_)                                                                                                   \
-    do {                                                                                                                      \
-        hipLaunchKernelGGL((sas_fwd_pre_kernel<D_, TM_>), dim3(n_max), dim3(kBlock), 0, stream, x, B, T, n_heads, P, sqrt_dk, qkv, \
-                           wgmax);                                                                                            \
-        WR_LAUNCH_CHECK("sas_fwd_pre_kernel");                                                                                \
-        hipLaunchKernelGGL((sas_fwd_main_kernel<D_, TM_>), dim3((unsigned)B), dim3(kBlock), 0, stream, x, B, T, n_heads, P, sqrt_dk, \
-                           dr, qkv, wgmax, n_max, out, gmax);                                                                 \
-        WR_LAUNCH_CHECK("sas_fwd_main_kernel");                                                                               \
-    } while (0)
-    WR_SAS_DISPATCH(D, T, WR_SAS_FWD);
-#undef WR_SAS_FWD
-    return WR_OK;
+                        void *stream) {
+    return sas_fwd<true>("wr_sasblock_fwd", x, B, T, D, d_ff, n_heads, params, p, seed, training, nullptr, nullptr, out, gmax,
+                         workspace, workspace_bytes, stream);
 }
 
 int32_t wr_sasblock_bwd(const float *x, const float *grad_out, int64_t B, int32_t T, int32_t D, int32_t d_ff, int32_t n_heads,
                         const float *const *params, float p, uint64_t seed, int32_t training, const float *gmax, float *gx,
-                        float *gparams, void *workspace, int64_t workspace_bytes, void *stream_) {
-    int32_t rc = sas_check("wr_sasblock_bwd", B, T, D, d_ff, n_heads);
-    if (rc != WR_OK) return rc;
-    WR_REQUIRE(x && grad_out && gmax && gx && gparams, WR_E_NULL, "wr_sasblock_bwd: NULL argument");
-    WR_REQUIRE(aligned16(x) && aligned16(grad_out) && aligned16(gx) && aligned16(gparams), WR_E_ALIGN,
-               "wr_sasblock_bwd: x, grad_out, gx and gparams must be 16-byte aligned");
-    SasParams P;
-    if ((rc = sas_check_params("wr_sasblock_bwd", params, P)) != WR_OK) return rc;
-    SasDrop dr;
-    if ((rc = sas_drop_of("wr_sasblock_bwd", p, seed, training, dr)) != WR_OK) return rc;
-    SasLayout L;
-    sas_layout(B, T, D, L);
-    if ((rc = check_workspace("wr_sasblock_bwd", workspace, workspace_bytes, L.total)) != WR_OK) return rc;
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    float *part = reinterpret_cast<float *>(reinterpret_cast<char *>(workspace) + L.part);
-    const int n_wg = (int)(B < kSasBwdWg ? B : kSasBwdWg), n_par = 5 * D * D + 9 * D;
-    const float sqrt_dk = sqrtf((float)(D / n_heads));
-#define WR_SAS_BWD(D_, TM_)                                                                                                    \
-    hipLaunchKernelGGL((sas_bwd_kernel<D_, TM_>), dim3(n_wg), dim3(kBlock), 0, stream, x, grad_out, B, T, n_heads, P, sqrt_dk, dr, \
-                       gmax, gx, part)
-    WR_SAS_DISPATCH(D, T, WR_SAS_BWD);
-#undef WR_SAS_BWD
-    WR_LAUNCH_CHECK("sas_bwd_kernel");
-    hipLaunchKernelGGL(sas_fold_kernel, dim3((n_par + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, part, n_wg, n_par, gparams);
-    WR_LAUNCH_CHECK("sas_fold_kernel");
-    return WR_OK;
+                        float *gparams, void *workspace, int64_t workspace_bytes, void *stream) {
+    return sas_bwd<true>("wr_sasblock_bwd", x, grad_out, B, T, D, d_ff, n_heads, params, p, seed, training, nullptr, nullptr, gmax,
+                         gx, gparams, workspace, workspace_bytes, stream);
+}
+
+int32_t wr_sasblock_fwd_keys(const float *x, int64_t B, int32_t T, int32_t D, int32_t d_ff, int32_t n_heads,
+                             const float *const *params, float p, uint64_t seed, int32_t training, float *out, float *gmax,
+                             void *workspace, int64_t workspace_bytes, void *stream, const int64_t *key_len, int32_t *err_word) {
+    return sas_fwd<false>("wr_sasblock_fwd_keys", x, B, T, D, d_ff, n_heads, params, p, seed, training, key_len, err_word, out, gmax,
+                          workspace, workspace_bytes, stream);
+}
+
+int32_t wr_sasblock_bwd_keys(const float *x, const float *grad_out, int64_t B, int32_t T, int32_t D, int32_t d_ff, int32_t n_heads,
+                             const float *const *params, float p, uint64_t seed, int32_t training, const float *gmax, float *gx,
+                             float *gparams, void *workspace, int64_t workspace_bytes, void *stream, const int64_t *key_len,
+                             int32_t *err_word) {
+    return sas_bwd<false>("wr_sasblock_bwd_keys", x, grad_out, B, T, D, d_ff, n_heads, params, p, seed, training, key_len, err_word,
+                          gmax, gx, gparams, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -1355,18 +1355,26 @@ def _sasblock_call_args(x, params, n_heads):
 
 
 class _SasBlock(torch.autograd.Function):
-    """wr_sasblock_fwd / wr_sasblock_bwd: saves x and the call's score maximum, nothing else"""
+    """wr_sasblock_fwd / wr_sasblock_bwd (key_len None) or their _keys variants: saves x and the call's score maximum, nothing
+    else"""
 
     @staticmethod
-    def forward(ctx, x, n_heads, p, seed, training, *params):
+    def forward(ctx, x, n_heads, p, seed, training, key_len, err, *params):
         x = _req(x.detach().contiguous(), torch.float32, "x", 3)
         params = [t.detach() for t in params]
         B, T, D, d_ff, ptrs, ws = _sasblock_call_args(x, params, n_heads)
         out = torch.empty_like(x)
         gmax = torch.empty(1, dtype=torch.float32, device=x.device)
-        abi.check(abi.lib().wr_sasblock_fwd(_p(x), B, T, D, d_ff, int(n_heads), _addr(ptrs), float(p), int(seed), int(bool(training)),
-                                            _p(out), _p(gmax), _p(ws), ws.numel(), _stream()), "wr_sasblock_fwd")
+        L = abi.lib()
+        if key_len is None:
+            abi.check(L.wr_sasblock_fwd(_p(x), B, T, D, d_ff, int(n_heads), _addr(ptrs), float(p), int(seed), int(bool(training)),
+                                        _p(out), _p(gmax), _p(ws), ws.numel(), _stream()), "wr_sasblock_fwd")
+        else:
+            abi.check(L.wr_sasblock_fwd_keys(_p(x), B, T, D, d_ff, int(n_heads), _addr(ptrs), float(p), int(seed),
+                                             int(bool(training)), _p(out), _p(gmax), _p(ws), ws.numel(), _stream(), _p(key_len),
+                                             _p(err)), "wr_sasblock_fwd_keys")
         ctx.save_for_backward(x, gmax, *params)
+        ctx.key_len = key_len
         ctx.conf = (int(n_heads), float(p), int(seed), int(bool(training)))
         return out
 
@@ -1379,13 +1387,19 @@ class _SasBlock(torch.autograd.Function):
         B, T, D, d_ff, ptrs, ws = _sasblock_call_args(x, params, n_heads)
         gx = torch.empty_like(x)
         packed = torch.empty(sum(t.numel() for t in params), dtype=torch.float32, device=x.device)
-        abi.check(abi.lib().wr_sasblock_bwd(_p(x), _p(grad_out), B, T, D, d_ff, n_heads, _addr(ptrs), p, seed, training, _p(gmax),
-                                            _p(gx), _p(packed), _p(ws), ws.numel(), _stream()), "wr_sasblock_bwd")
+        L = abi.lib()
+        if ctx.key_len is None:
+            abi.check(L.wr_sasblock_bwd(_p(x), _p(grad_out), B, T, D, d_ff, n_heads, _addr(ptrs), p, seed, training, _p(gmax),
+                                        _p(gx), _p(packed), _p(ws), ws.numel(), _stream()), "wr_sasblock_bwd")
+        else:       # the forward has reported a bad length already
+            abi.check(L.wr_sasblock_bwd_keys(_p(x), _p(grad_out), B, T, D, d_ff, n_heads, _addr(ptrs), p, seed, training, _p(gmax),
+                                             _p(gx), _p(packed), _p(ws), ws.numel(), _stream(), _p(ctx.key_len), None),
+                      "wr_sasblock_bwd_keys")
         views, o = [], 0
         for t in params:                                  # the packed gradient, returned as views
             views.append(packed[o:o + t.numel()].view(t.shape))
             o += t.numel()
-        return (gx, None, None, None, None, *views)
+        return (gx, None, None, None, None, None, None, *views)
 
 
 def sasblock_params(block):
@@ -1394,11 +1408,95 @@ def sasblock_params(block):
     return [sd[n] for n in SASBLOCK_PARAMS]
 
 
-def sasrec_block(x, block_module, n_heads, p, seed, training):
+def sasrec_block(x, block_module, n_heads, p, seed, training, key_lengths=None, err_word=None):
     """One whole transformer block of SASRec (sasrec._Block / layers.py:8-86) on x [B, T, D] by the fused HIP kernels, under
     autograd: two launches forward, two backward.  Dropout p is applied iff `training`, with the counter-based mask of
-    wr_sasblock.hip keyed by `seed` (not torch's generator); the backward recomputes it."""
-    return _SasBlock.apply(x, int(n_heads), float(p), int(seed) & 0xFFFFFFFFFFFFFFFF, bool(training), *sasblock_params(block_module))
+    wr_sasblock.hip keyed by `seed` (not torch's generator); the backward recomputes it.
+    key_lengths None: the causal mask.  key_lengths int64 [B] on the device: every query keeps the keys j < key_lengths[b]
+    (ContraRec's BERT4RecEncoder); a length outside [1, T] is clamped and ORs 1 into `err_word` (an int32 (1,) device tensor the
+    caller clears and reads, or None) — no host round trip here."""
+    if key_lengths is not None:
+        key_lengths = _idx64(key_lengths.reshape(-1), "key_lengths")
+        if key_lengths.numel() != x.shape[0]:
+            raise ValueError("key_lengths must hold one length per sequence (got %d for B=%d)" % (key_lengths.numel(), x.shape[0]))
+        if err_word is not None:
+            _req(err_word, torch.int32, "err_word")
+    return _SasBlock.apply(x, int(n_heads), float(p), int(seed) & 0xFFFFFFFFFFFFFFFF, bool(training), key_lengths, err_word,
+                           *sasblock_params(block_module))
+
+
+# ----------------------------------------------------------------------------------------------- supervised contrastive loss (K15)
+_SUPCON_WS = {}         # (device, stream, B, D) -> workspace: nothing is allocated after the first call of a shape
+
+
+def supcon_supports(D):
+    """embedding sizes wr_supcon_loss_grad takes (wr_supcon_supported)"""
+    return bool(abi.lib().wr_supcon_supported(int(D)))
+
+
+SUPCON_MAX_ROWS = 1 << 15
+
+
+def supcon_workspace_bytes(B, D):
+    return abi.check_size(abi.lib().wr_supcon_workspace_bytes(int(B), int(D)), "wr_supcon_workspace_bytes")
+
+
+def supcon_loss_grad(F, labels, tau, weight=1.0, *, loss=None, grads=True):
+    """ContraRec's supervised contrastive loss (ContraLoss, ContraRec.py:141-204, as written: double shift by the row maximum,
+    both + 1e-10) over F [2B, D] — raw, unnormalised; rows 0..B-1 view a, rows B..2B-1 view b, row r labelled labels[r mod B] —
+    and its gradient w.r.t. F, without a [2B, 2B] array (wr_supcon_loss_grad).  `loss`: a (1,) device tensor to ADD weight * loss
+    to (None = a fresh one).  `grads=False`: loss only, same bits.  Returns (loss, gF)."""
+    _req(F, torch.float32, "F", 2)
+    lab = _idx64(labels.reshape(-1), "labels")
+    N, D = int(F.shape[0]), int(F.shape[1])
+    B = lab.numel()
+    if N != 2 * B:
+        raise ValueError("F must hold 2 * len(labels) rows (got %d rows, %d labels)" % (N, B))
+    if not supcon_supports(D) or B < 1 or N > SUPCON_MAX_ROWS:
+        raise abi.WhisprRecHipError("supcon_loss_grad does not support D=%d, B=%d (D in {32, 64, 128}, 1 <= B, 2 B <= %d)"
+                                    % (D, B, SUPCON_MAX_ROWS))
+    if not (float(tau) > 0.0):
+        raise ValueError("tau must be positive (got %r)" % (tau,))
+    dev = F.device
+    accumulate = loss is not None
+    if accumulate:
+        _req(loss, torch.float32, "loss")
+        if loss.numel() != 1:
+            raise ValueError("loss must hold one element")
+    else:
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+    gF = torch.empty((N, D), dtype=torch.float32, device=dev) if grads else None
+    key = (str(dev), torch.cuda.current_stream(dev).cuda_stream, B, D)
+    ws = _SUPCON_WS.get(key)
+    if ws is None:
+        ws = _SUPCON_WS[key] = torch.empty(supcon_workspace_bytes(B, D), dtype=torch.uint8, device=dev)
+    abi.check(abi.lib().wr_supcon_loss_grad(_p(F), B, D, _p(lab), float(tau), _p(loss), int(accumulate), float(weight), _p(gF), None,
+                                            _p(ws), ws.numel(), _stream()), "wr_supcon_loss_grad")
+    return loss, gF
+
+
+def supcon_release_workspaces():
+    _SUPCON_WS.clear()
+
+
+class _SupCon(torch.autograd.Function):
+    """loss and gradient in one call of wr_supcon_loss_grad; the backward scales the stored gradient"""
+
+    @staticmethod
+    def forward(ctx, F, labels, tau):
+        loss, gF = supcon_loss_grad(F.detach().contiguous(), labels, tau)
+        ctx.save_for_backward(gF)
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        (gF,) = ctx.saved_tensors
+        return gF * grad_out, None, None
+
+
+def supcon_loss(F, labels, tau):
+    """supcon_loss_grad under autograd: a 0-d loss whose backward hands F the kernel's gradient"""
+    return _SupCon.apply(F, labels, float(tau))
 
 
 # ----------------------------------------------------------------------------------------------- optimizers

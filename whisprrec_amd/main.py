@@ -18,9 +18,10 @@ import sys
 import numpy as np
 import torch
 
-from . import bprmf, lightgcn, reader, runner, sasrec, sgl
+from . import bprmf, contrarec, lightgcn, reader, runner, sasrec, sgl
 
-MODELS = {"BPRMF": bprmf.BPRMF, "LightGCN": lightgcn.LightGCN, "SGL": sgl.SGL, "SASRec": sasrec.SASRec}
+MODELS = {"BPRMF": bprmf.BPRMF, "LightGCN": lightgcn.LightGCN, "SGL": sgl.SGL, "SASRec": sasrec.SASRec,
+          "ContraRec": contrarec.ContraRec}
 READERS = {"BaseReader": reader.BaseReader, "SeqReader": reader.SeqReader}
 RUNNERS = {"BaseRunner": runner.BaseRunner, "HipRunner": runner.HipRunner}
 

@@ -663,7 +663,10 @@ def make_hip_runner(base_runner_cls):
         def fit(self, dataset, epoch=-1):
             model = dataset.model
             sequential = "position" in dataset.data
-            if not hasattr(model, "user_num") or (sequential and not hasattr(model, "history_max")):
+            # a model whose training rows carry more than (user, positive, negative, history) — ContraRec's two augmented views,
+            # drawn sample by sample from NumPy's global stream — keeps the reference's DataLoader loop
+            if not hasattr(model, "user_num") or (sequential and not hasattr(model, "history_max")) or \
+                    getattr(model, "per_sample_feed", False):
                 return base_runner_cls.fit(self, dataset, epoch)
             dev = next(model.parameters()).device
             model.train()
