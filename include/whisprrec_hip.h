@@ -911,6 +911,41 @@ int32_t wr_supcon_loss_grad(const float *F, int64_t B, int32_t D, const int64_t 
                             int32_t accumulate, float weight, float *gF, int32_t *err_word, void *workspace,
                             int64_t workspace_bytes, void *stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * K16  BUIR's bootstrap loss (src/models/general/BUIR.py:76-97) and every gradient of it in one call.  The four tables are
+ *      [n_users | n_items, D] fp32 row-major, W [D, D] (nn.Linear: out x in) and b [D] the shared predictor, users / items
+ *      int64 [B].  For sample k with online rows x_u, x_i and target rows t_u, t_i, p = W x + b, z^ = z / max(|z|, 1e-12):
+ *   l_k  = 4 - 2 <p_u^, t_i^> - 2 <p_i^, t_u^>        loss = mean_k l_k
+ *   g_pu = (-2/B) (t_i^ - p_u^ <p_u^, t_i^>) / |p_u|  (g_pi likewise)        gU[k] = W^T g_pu,  gI[k] = W^T g_pi
+ *   gW   = sum_k g_pu x_u^T + g_pi x_i^T               gb = sum_k g_pu + g_pi
+ *   - Targets are constants.  gU / gI [B, D] are PER-SAMPLE gradients w.r.t. the gathered online rows (a row that occurs twice
+ *     has two entries: scatter-add them for the dense table gradient); gW [D, D], gb [D], loss [1] are fully written.
+ *     gU == NULL: loss only (gI, gW, gb are then ignored), with the bits of the full call's loss.
+ *   - A predictor output with |p| < 1e-12 is divided by 1e-12 instead of |p| and keeps the projection term: torch passes no
+ *     gradient through the clamped norm there.  That regime is not claimed; a zero TARGET row is exact (term 2, gradient 0).
+ *   - The three products ([2B, D] x [D, D] forward, the row gradients, the weight gradient) are fp32 k-ordered chains of
+ *     v_mfma_f32_32x32x2_f32 (wr_score_tiles.h); rows are gathered straight from the tables, no [B, D] copies.
+ *   - Determinism: no float atomics.  Workgroup w (128 samples) writes its partial gW, gb and loss sum into the workspace; a
+ *     second launch folds the partials in workgroup order.  The grid depends on (B, D) only: same inputs, same bits on any
+ *     device.
+ *   - An id outside [0, n_users) / [0, n_items) is clamped into the table and ORs 1 into err_word (int32 on the device, may be
+ *     NULL; the caller clears and reads it): no fault follows from an unsafe id.
+ *   - D in {32, 64, 128} (wr_buir_supported), 1 <= B <= 2^22; anything else, a NULL or misaligned (16 B) pointer or a short
+ *     workspace (< wr_buir_workspace_bytes(B, D), 16-byte aligned) is refused before any launch.
+ *   - No host round trip, no allocation. */
+int32_t wr_buir_supported(int32_t D);
+int64_t wr_buir_workspace_bytes(int64_t B, int32_t D);
+int32_t wr_buir_loss_grad(const float *user_online, const float *item_online, const float *user_target,
+                          const float *item_target, int64_t n_users, int64_t n_items, int32_t D, const float *W, const float *b,
+                          const int64_t *users, const int64_t *items, int64_t B, float *loss, float *gU, float *gI, float *gW,
+                          float *gb, int32_t *err_word, void *workspace, int64_t workspace_bytes, void *stream);
+
+/* K17  BUIR's momentum update of a target table (BUIR.py:69-74), in place and in one pass of 16-byte accesses:
+ *      t[i] = t[i] * m + o[i] * one_minus_m, i < n — two products and one sum, each rounded (never contracted to an FMA), which
+ *      is what torch's `t * m + o * (1. - m)` computes; the caller forms 1 - m in double and narrows it.  Every element is
+ *      rewritten (t m + t (1 - m) is not t in fp32).  t and o 16-byte aligned, n >= 1. */
+int32_t wr_ema_update(float *t, const float *o, int64_t n, float m, float one_minus_m, void *stream);
+
 /* LightGCN.predict's per-batch tail in two launches (src/models/general/LightGCN.py:156-175, src/utils/loss.py:37-39,94-98):
  *   loss[0] = mean_b( -log(1e-10 + sigmoid(<Ua[u_b], Ia[p_b]> - <Ua[u_b], Ia[n_b]>)) )
  *             + reg_weight * (||U0[u]||_F + ||I0[p]||_F + ||I0[n]||_F) / B

@@ -194,6 +194,11 @@ SIGNATURES = {
     "wr_supcon_supported": (c_i32, [c_i32]),
     "wr_supcon_workspace_bytes": (c_i64, [c_i64, c_i32]),
     "wr_supcon_loss_grad": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_f32, c_vp, c_i32, c_f32, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "wr_buir_supported": (c_i32, [c_i32]),
+    "wr_buir_workspace_bytes": (c_i64, [c_i64, c_i32]),
+    "wr_buir_loss_grad": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp,
+                                  c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "wr_ema_update": (c_i32, [c_vp, c_vp, c_i64, c_f32, c_f32, c_vp]),
     "wr_lightgcn_loss_workspace_bytes": (c_i64, [c_i64]),
     "wr_lightgcn_loss": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_vp, c_vp, c_vp, c_i64, c_f32, c_vp, c_vp, c_vp,
                                  c_i64, c_vp]),

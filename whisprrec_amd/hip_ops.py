@@ -1499,6 +1499,109 @@ def supcon_loss(F, labels, tau):
     return _SupCon.apply(F, labels, float(tau))
 
 
+# ----------------------------------------------------------------------------------------------- BUIR (K16, K17)
+_BUIR_WS = {}           # (device, stream, B, D) -> workspace: nothing is allocated after the first call of a shape
+
+
+def buir_supports(D):
+    """embedding sizes wr_buir_loss_grad takes (wr_buir_supported)"""
+    return bool(abi.lib().wr_buir_supported(int(D)))
+
+
+BUIR_MAX_BATCH = 1 << 22
+
+
+def buir_workspace_bytes(B, D):
+    return abi.check_size(abi.lib().wr_buir_workspace_bytes(int(B), int(D)), "wr_buir_workspace_bytes")
+
+
+def buir_loss_grad(user_online_w, item_online_w, user_target_w, item_target_w, W, b, users, items, *, grads=True, err_word=None):
+    """BUIR's bootstrap loss (BUIR.py:76-97) over the batch (users, items) and every gradient of it, in one call of
+    wr_buir_loss_grad.  Returns (loss (1,), gU [B, D], gI [B, D], gW [D, D], gb [D]): gU / gI are PER-SAMPLE gradients w.r.t. the
+    gathered online rows, targets are constants.  `grads=False`: loss only (the other four are None), same bits.  An id outside
+    its table is clamped and ORs 1 into `err_word` (an int32 (1,) device tensor the caller clears and reads, or None)."""
+    for t, nm in ((user_online_w, "user_online_w"), (item_online_w, "item_online_w"), (user_target_w, "user_target_w"),
+                  (item_target_w, "item_target_w"), (W, "W")):
+        _req(t, torch.float32, nm, 2)
+    _req(b, torch.float32, "b", 1)
+    uu, ii = _idx64(users.reshape(-1), "users"), _idx64(items.reshape(-1), "items")
+    B, D = uu.numel(), int(W.shape[0])
+    if ii.numel() != B:
+        raise ValueError("users and items must hold one id per sample (got %d and %d)" % (B, ii.numel()))
+    if user_target_w.shape != user_online_w.shape or item_target_w.shape != item_online_w.shape:
+        raise ValueError("a target table must have the shape of its online table")
+    if tuple(W.shape) != (D, D) or b.numel() != D or user_online_w.shape[1] != D or item_online_w.shape[1] != D:
+        raise ValueError("W must be [D, D] and b [D] with D the embedding size of the tables")
+    if not buir_supports(D) or B < 1 or B > BUIR_MAX_BATCH:
+        raise abi.WhisprRecHipError("buir_loss_grad does not support D=%d, B=%d (D in {32, 64, 128}, 1 <= B <= %d)"
+                                    % (D, B, BUIR_MAX_BATCH))
+    if err_word is not None:
+        _req(err_word, torch.int32, "err_word")
+    dev = W.device
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    gU = gI = gW = gb = None
+    if grads:
+        gU = torch.empty((B, D), dtype=torch.float32, device=dev)
+        gI = torch.empty((B, D), dtype=torch.float32, device=dev)
+        gW = torch.empty((D, D), dtype=torch.float32, device=dev)
+        gb = torch.empty(D, dtype=torch.float32, device=dev)
+    key = (str(dev), torch.cuda.current_stream(dev).cuda_stream, B, D)
+    ws = _BUIR_WS.get(key)
+    if ws is None:
+        ws = _BUIR_WS[key] = torch.empty(buir_workspace_bytes(B, D), dtype=torch.uint8, device=dev)
+    abi.check(abi.lib().wr_buir_loss_grad(_p(user_online_w), _p(item_online_w), _p(user_target_w), _p(item_target_w),
+                                          user_online_w.shape[0], item_online_w.shape[0], D, _p(W), _p(b), _p(uu), _p(ii), B, _p(loss),
+                                          _p(gU), _p(gI), _p(gW), _p(gb), _p(err_word), _p(ws), ws.numel(), _stream()),
+              "wr_buir_loss_grad")
+    return loss, gU, gI, gW, gb
+
+
+class _BuirLoss(torch.autograd.Function):
+    """loss and gradients in one call of wr_buir_loss_grad; the backward scales the stored gradients into NEW tensors (a second
+    backward gives the same gradients) and scatter-adds the per-sample rows into dense table gradients"""
+
+    @staticmethod
+    def forward(ctx, user_online_w, item_online_w, W, b, user_target_w, item_target_w, users, items, err_word, need):
+        loss, gU, gI, gW, gb = buir_loss_grad(user_online_w.detach(), item_online_w.detach(), user_target_w.detach(),
+                                              item_target_w.detach(), W.detach(), b.detach(), users, items, grads=need,
+                                              err_word=err_word)
+        if need:
+            # the kernel read clamped ids; the scatter below must not leave the tables either
+            uu = users.reshape(-1).clamp(0, user_online_w.shape[0] - 1)
+            ii = items.reshape(-1).clamp(0, item_online_w.shape[0] - 1)
+            ctx.save_for_backward(gU, gI, gW, gb, uu, ii)
+            ctx.shapes = (tuple(user_online_w.shape), tuple(item_online_w.shape))
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        gU, gI, gW, gb, uu, ii = ctx.saved_tensors
+        su, si = ctx.shapes
+        dU = scatter_add_rows(torch.zeros(su, dtype=torch.float32, device=gU.device), uu, gU * grad_out)
+        dI = scatter_add_rows(torch.zeros(si, dtype=torch.float32, device=gI.device), ii, gI * grad_out)
+        return dU, dI, gW * grad_out, gb * grad_out, None, None, None, None, None, None
+
+
+def buir_loss(user_online_w, item_online_w, user_target_w, item_target_w, W, b, users, items, err_word=None):
+    """buir_loss_grad under autograd: a 0-d loss whose backward hands the two online tables dense gradients (scatter_add_rows of
+    the per-sample rows) and the predictor its own.  Under torch.no_grad(), or when nothing requires a gradient: loss only."""
+    need = torch.is_grad_enabled() and any(t.requires_grad for t in (user_online_w, item_online_w, W, b))
+    return _BuirLoss.apply(user_online_w, item_online_w, W, b, user_target_w, item_target_w, users, items, err_word, need)
+
+
+def ema_update_(target, online, momentum):
+    """target = target * momentum + online * (1. - momentum), in place and in one pass (wr_ema_update): the three roundings of
+    BUIR._update_target (BUIR.py:71), 1 - momentum formed in double as Python forms it.  Returns target."""
+    _req(target, torch.float32, "target")
+    _req(online, torch.float32, "online")
+    if target.shape != online.shape:
+        raise ValueError("target and online must have one shape (got %s and %s)" % (tuple(target.shape), tuple(online.shape)))
+    if target.numel():
+        abi.check(abi.lib().wr_ema_update(_p(target), _p(online), target.numel(), float(momentum), float(1. - float(momentum)),
+                                          _stream()), "wr_ema_update")
+    return target
+
+
 # ----------------------------------------------------------------------------------------------- optimizers
 def sgd_dense(tab, grad, lr, l2=0.0, stamp=None, step_id=0):
     abi.check(abi.lib().wr_sgd_dense(_p(_req(tab, torch.float32, "tab", 2)), tab.shape[0], tab.shape[1],
