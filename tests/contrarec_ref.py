@@ -24,8 +24,11 @@ from sasblock_ref import PARAMS, _ln_bwd, _ln_fwd, figures, fmt, group_of, rel_e
 # ------------------------------------------------------------------------------------------------ shapes and tolerances
 # (B, T, D, heads); the first is g12's batch with the state of encoder.transformer_block.0
 BLOCK_SHAPES = [(96, 20, 64, 2), (3, 1, 64, 2), (5, 7, 32, 2), (2, 33, 64, 2), (130, 64, 64, 1), (37, 20, 32, 4)]
-# (B, D, tau, distinct labels); a quarter of the rows are identical in both views
-LOSS_SHAPES = [(3, 32, 0.2, 2), (64, 64, 0.2, 10), (65, 64, 0.2, 20), (200, 32, 0.05, 30), (256, 64, 0.2, 40), (64, 128, 0.05, 500)]
+# (B, D, tau, distinct labels); a quarter of the rows are identical in both views.  The last three give every column chunk of the
+# kernel two tiles and the last chunk one full tile and a ragged one (the second tile, the buffer swap): 2B rows above 2048 at
+# D <= 64, above 1448 at D = 128
+LOSS_SHAPES = [(3, 32, 0.2, 2), (64, 64, 0.2, 10), (65, 64, 0.2, 20), (200, 32, 0.05, 30), (256, 64, 0.2, 40), (64, 128, 0.05, 500),
+               (1140, 64, 0.2, 100), (760, 128, 0.05, 500), (1130, 32, 0.2, 60)]
 
 # Largest floor of each figure over the shapes: stock fp32 torch (sasrec._Block with the [B, 1, 1, T] mask; contrarec.contra_loss
 # over F.normalize) against float64, on a CPU.

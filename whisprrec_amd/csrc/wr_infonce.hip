@@ -22,12 +22,10 @@
 //   scatter     rows named by the batch: gA[id] = sum of the per-position gradients, gB[id] += sum of the positive terms, by
 //               the owner position, in ascending position order
 // No float atomics anywhere: every sum has a fixed order, the results are bitwise reproducible.  No host round trip.
-#include "wr_row_team.h"
-#include "wr_score_tiles.h"
+#include "wr_pair_pass.h"
 
 namespace wr {
 
-constexpr int kNceRows = kScoreRows;      // resident rows per workgroup (32 per wave)
 constexpr int64_t kNceTargetWg = 1024;    // workgroups a pass aims at when it splits the streamed side into chunks
 
 // ------------------------------------------------------------------------------------------------ prep
@@ -73,101 +71,39 @@ __global__ __launch_bounds__(kBlock) void nce_prep_q_kernel(const float *__restr
 }
 
 // ------------------------------------------------------------------------------------------------ the two GEMM passes
-// Resident rows R [nr, D] (128 per workgroup, 32 per wave, in registers as the B operand), streamed rows T [nt, D] in tiles
-// of TS through LDS as the A operand:  s = <T[i], R[j]> (k-ordered chain),  w_ij = exp2((s - 1) * escale) * tscale[i],
-//     zpart[chunk][j]    = sum_i w_ij                      (zpart may be NULL)
-//     part[chunk][j][:]  = sum_i w_ij * T[i][:]            (GRAD only)
+// pair_pass (wr_pair_pass.h) with the softmax weights: for the streamed row i and the resident row j,
+//     w_ij = exp2((s - 1) * escale) * tscale[i],     zpart[chunk][j] = sum_i w_ij     (zpart may be NULL)
 // over the streamed rows i of the chunk blockIdx.y.  tscale NULL = 1.  Streamed rows past the end weigh 0.
+// The policy is a local struct of the kernel so that it names the kernel's LDS array itself: reached through a pointer member the
+// same reads compile to other address arithmetic and five more VGPRs in the gradient pass.
 template <int KS, int TS, bool GRAD>
 __global__ __launch_bounds__(kBlock, 2) void nce_pass_kernel(const float *__restrict__ R, int64_t nr, const float *__restrict__ T,
                                                             int64_t nt, const float *__restrict__ tscale, float escale,
                                                             int64_t chunk_rows, float *__restrict__ part,
                                                             float *__restrict__ zpart) {
-    constexpr int D = 2 * KS, LDW = D + 1, C = TS / 32, NB = D / 32;
-    __shared__ float it[2][TS * LDW];
-    __shared__ float sc[2][TS];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int col = lane & 31, half = lane >> 5;
-    const int64_t e0 = (int64_t)blockIdx.x * kNceRows;
-    const int64_t c0 = (int64_t)blockIdx.y * chunk_rows;
-    const int64_t c1 = (c0 + chunk_rows < nt) ? c0 + chunk_rows : nt;
-    // B[k = 2s + (lane>>5)][j = lane&31] of this wave's slab of resident rows
-    float a[KS];
-    {
-        const int64_t e = e0 + wave * 32 + col;
-        const float *rrow = R + ((e < nr) ? e : 0) * (int64_t)D + half;
-#pragma unroll
-        for (int s = 0; s < KS; ++s) a[s] = (e < nr) ? rrow[2 * s] : 0.f;
-    }
-    f32x16 out[NB];
-#pragma unroll
-    for (int b = 0; b < NB; ++b) out[b] = f32x16{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    float z = 0.f;
-    TileStager<D, TS> stager;
-    float sstage = 0.f;
-    auto fetch = [&](int64_t j0) {
-        stager.fetch(T, j0, c1);
-        if (threadIdx.x < TS) {
-            const int64_t r = j0 + threadIdx.x;
-            sstage = (r < c1) ? (tscale != nullptr ? tscale[r] : 1.0f) : 0.f;
+    __shared__ float sc[2][TS];                                         // the scale of every row of the two tiles
+    struct Policy {
+        const float *__restrict__ tscale;
+        float escale;
+        float *__restrict__ zpart;
+        float sstage = 0.f, z = 0.f;
+
+        __device__ __forceinline__ void start(int64_t, int64_t, int64_t) {}
+        __device__ __forceinline__ void fetch_side(int64_t r, bool in) { sstage = in ? (tscale != nullptr ? tscale[r] : 1.0f) : 0.f; }
+        __device__ __forceinline__ void deposit_side(int buf) { sc[buf][threadIdx.x] = sstage; }
+        __device__ __forceinline__ float weight(float s, int tr, int64_t, int64_t, int buf) {
+            const float w = __builtin_amdgcn_exp2f((s - 1.0f) * escale) * sc[buf][tr];
+            z += w;
+            return w;
         }
-    };
-    auto deposit = [&](int buf) {
-        stager.deposit(it[buf]);
-        if (threadIdx.x < TS) sc[buf][threadIdx.x] = sstage;
-    };
-    fetch(c0);
-    deposit(0);
-    __syncthreads();
-    int buf = 0;
-    for (int64_t j0 = c0; j0 < c1; j0 += TS, buf ^= 1) {
-        const bool more = j0 + TS < c1;
-        if (more) fetch(j0 + TS);                                       // global loads fly while the matrix cores work
-        // acc[c][reg] = score(streamed row c*32 + acc_row(reg, half), resident row lane&31)
-        f32x16 acc[C];
-        score_tiles<KS, C, LDW, true>(a, &it[buf][col * LDW + half], acc);   // A[i = lane&31][k = 2s + (lane>>5)] of block 0
-#pragma unroll
-        for (int c = 0; c < C; ++c) {
-#pragma unroll
-            for (int reg = 0; reg < 16; ++reg) {
-                const float w = __builtin_amdgcn_exp2f((acc[c][reg] - 1.0f) * escale) * sc[buf][c * 32 + acc_row(reg, half)];
-                z += w;
-                acc[c][reg] = w;
+        __device__ __forceinline__ void finish(int64_t e, int64_t nr, int half) {
+            z += __shfl_xor(z, 32, 64);
+            if (zpart != nullptr && half == 0) {
+                if (e < nr) zpart[(int64_t)blockIdx.y * nr + e] = z;
             }
         }
-        if constexpr (GRAD) {
-            // out[j][d] += sum_i w_ij T[i][d]: step `reg` of the k loop pairs the two streamed rows the two half-waves
-            // hold in accumulator register `reg` — the weights are already where the A operand wants them
-#pragma unroll
-            for (int c = 0; c < C; ++c) {
-#pragma unroll
-                for (int reg = 0; reg < 16; ++reg) {
-                    // B[k = half][j = d = lane&31 (+ 32 b)]
-                    const float *brow = &it[buf][(c * 32 + acc_row(reg, half)) * LDW + col];
-#pragma unroll
-                    for (int b = 0; b < NB; ++b)
-                        out[b] = __builtin_amdgcn_mfma_f32_32x32x2f32(acc[c][reg], brow[b * 32], out[b], 0, 0, 0);
-                }
-            }
-        }
-        if (more) deposit(buf ^ 1);                                     // the other buffer was last read one barrier ago
-        __syncthreads();
-    }
-    z += __shfl_xor(z, 32, 64);                                         // the two half-waves hold disjoint streamed rows
-    if (zpart != nullptr && half == 0) {
-        const int64_t e = e0 + wave * 32 + col;
-        if (e < nr) zpart[(int64_t)blockIdx.y * nr + e] = z;
-    }
-    if constexpr (GRAD) {
-#pragma unroll
-        for (int b = 0; b < NB; ++b) {
-#pragma unroll
-            for (int reg = 0; reg < 16; ++reg) {
-                const int64_t e = e0 + wave * 32 + acc_row(reg, half);
-                if (e < nr) part[((int64_t)blockIdx.y * nr + e) * D + b * 32 + col] = out[b][reg];
-            }
-        }
-    }
+    } P{tscale, escale, zpart};
+    pair_pass<KS, TS, GRAD>(P, R, nr, T, nt, chunk_rows, part);
 }
 
 // ------------------------------------------------------------------------------------------------ reductions
@@ -215,32 +151,6 @@ __global__ __launch_bounds__(kBlock) void nce_reduce_q_kernel(int64_t B, int D, 
     }
 }
 
-__global__ __launch_bounds__(kBlock) void nce_loss_kernel(const float *__restrict__ lterm, int64_t B, float weight, int accumulate,
-                                                          float *__restrict__ loss) {
-    __shared__ float scratch[kBlock / 64];
-    float v = 0.f;
-    for (int64_t i = threadIdx.x; i < B; i += kBlock) v += lterm[i];
-    const float r = block_sum(v, scratch);
-    if (threadIdx.x == 0) loss[0] = (accumulate ? loss[0] : 0.f) + weight * r;
-}
-
-// Per row of Bm: fold the chunk partials of sum_b softmax_bj q_b, scale by weight / tau, back through the normalisation
-__global__ __launch_bounds__(kBlock) void nce_reduce_k_kernel(int64_t n, int D, int64_t chunks, const float *__restrict__ part,
-                                                              const float *__restrict__ Kn, const float *__restrict__ invB,
-                                                              float wtau, float *__restrict__ gB) {
-    const int64_t t = (int64_t)blockIdx.x * kNceTeamsPerBlock + (threadIdx.x / kNceTeam);
-    const int l = threadIdx.x & (kNceTeam - 1);
-    const bool live = t < n;
-    const int64_t j = live ? t : 0;
-    const int D4 = D / 4;
-    NceRow H;
-    H.v[0] = H.v[1] = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int64_t c = 0; c < chunks; ++c) nce_add(H, nce_load(part + (c * n + j) * (int64_t)D, D4, l));
-    const NceRow k = nce_load(Kn + j * (int64_t)D, D4, l);
-    const NceRow g = nce_bwd(nce_axpby(H, wtau, H, 0.f), k, invB[j]);
-    if (live) nce_store(gB + j * (int64_t)D, D4, l, g);
-}
-
 // Rows named by the batch.  The owner of a row (its first position) sums the per-position rows of every position that
 // names it, in ascending position order, and is the only writer of that row: gA[id] = sum, gB[id] += sum.
 __global__ __launch_bounds__(kBlock) void nce_scatter_kernel(int64_t B, int D, const int64_t *__restrict__ cidx,
@@ -280,42 +190,37 @@ __global__ __launch_bounds__(kBlock) void nce_scatter_kernel(int64_t B, int D, c
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-static inline int nce_tile(int D) { return D <= 64 ? 64 : 32; }
-
-// split of the streamed side (nt rows) of a pass with nr resident rows: chunks * nr <= kNceTargetWg * kNceRows + nr + kNceRows
-static void nce_chunks(int64_t nr, int64_t nt, int TS, int64_t &chunks, int64_t &chunk_rows) {
-    const int64_t rb = (nr + kNceRows - 1) / kNceRows, tiles = (nt + TS - 1) / TS;
-    const int64_t want = (kNceTargetWg + rb - 1) / rb;
-    const int64_t ch = tiles < want ? tiles : want;
-    const int64_t tpc = (tiles + ch - 1) / ch;
-    chunks = (tiles + tpc - 1) / tpc;
-    chunk_rows = tpc * TS;
-}
-
-struct NceLayout {
-    int64_t Kn, invB, owner, Q, invA, cidx, dup, zpart, part, invZ, lterm, growA, growB, total;   // byte offsets
+// The partials are sized by the bound of pair_chunks, not by the split itself: every term is non-decreasing in n and in B.
+struct NceWs {
+    float *Kn, *invB;
+    int *owner;
+    float *Q, *invA;
+    int64_t *cidx;
+    int *dup;
+    float *zpart, *part, *invZ, *lterm, *growA, *growB;
+    int64_t total;
 };
 
-static void nce_layout(int64_t n, int64_t B, int32_t D, NceLayout &L) {
-    // every term is non-decreasing in n and in B; the partials are sized by the bound of nce_chunks, not by the split itself
-    const int64_t part_rows = kNceTargetWg * kNceRows + 2 * kNceRows + (n > B ? n : B);
-    const int64_t z_rows = kNceTargetWg * kNceRows + 2 * kNceRows + B;
-    int64_t o = 0;
-    auto take = [&](int64_t bytes) { const int64_t at = o; o += align_up(bytes, 256); return at; };
-    L.Kn = take(n * D * 4);
-    L.invB = take(n * 4);
-    L.owner = take(n * 4);
-    L.Q = take(B * D * 4);
-    L.invA = take(B * 4);
-    L.cidx = take(B * 8);
-    L.dup = take(B * 4);
-    L.zpart = take(z_rows * 4);
-    L.part = take(part_rows * D * 4);
-    L.invZ = take(B * 4);
-    L.lterm = take(B * 4);
-    L.growA = take(B * D * 4);
-    L.growB = take(B * D * 4);
-    L.total = o;
+static NceWs nce_carve(void *workspace, int64_t n, int64_t B, int32_t D) {
+    const int64_t part_rows = kNceTargetWg * kPairRows + 2 * kPairRows + (n > B ? n : B);
+    const int64_t z_rows = kNceTargetWg * kPairRows + 2 * kPairRows + B;
+    Carver c(workspace);
+    NceWs W;
+    W.Kn = c.take<float>(n * D);
+    W.invB = c.take<float>(n);
+    W.owner = c.take<int>(n);
+    W.Q = c.take<float>(B * D);
+    W.invA = c.take<float>(B);
+    W.cidx = c.take<int64_t>(B);
+    W.dup = c.take<int>(B);
+    W.zpart = c.take<float>(z_rows);
+    W.part = c.take<float>(part_rows * D);
+    W.invZ = c.take<float>(B);
+    W.lterm = c.take<float>(B);
+    W.growA = c.take<float>(B * D);
+    W.growB = c.take<float>(B * D);
+    W.total = c.bytes;
+    return W;
 }
 
 static inline bool nce_shape_ok(int64_t n, int64_t B) {
@@ -326,9 +231,9 @@ template <bool GRAD>
 static void nce_launch_pass(int32_t D, dim3 grid, hipStream_t stream, const float *R, int64_t nr, const float *T, int64_t nt,
                             const float *tscale, float escale, int64_t chunk_rows, float *part, float *zpart) {
 #define WR_NCE_PASS(KS_)                                                                                              \
-    hipLaunchKernelGGL((nce_pass_kernel<KS_, ((KS_) <= 32 ? 64 : 32), GRAD>), grid, dim3(kBlock), 0, stream, R, nr, T, nt, tscale, \
+    hipLaunchKernelGGL((nce_pass_kernel<KS_, pair_tile(2 * (KS_)), GRAD>), grid, dim3(kBlock), 0, stream, R, nr, T, nt, tscale, \
                        escale, chunk_rows, part, zpart)
-    WR_DISPATCH_KS(D, 16, 64, WR_NCE_PASS);                             // the tile height is nce_tile(D)
+    WR_DISPATCH_KS(D, 16, 64, WR_NCE_PASS);
 #undef WR_NCE_PASS
 }
 
@@ -343,9 +248,7 @@ int32_t wr_infonce_supported(int32_t D) { return (D == 32 || D == 64 || D == 128
 int64_t wr_infonce_workspace_bytes(int64_t n_rows, int64_t B, int32_t D) {
     WR_REQUIRE(wr_infonce_supported(D), WR_E_RANGE, "infonce supports D in {32, 64, 128}; got D=%d", D);
     WR_REQUIRE(nce_shape_ok(n_rows, B), WR_E_SHAPE, "infonce: n_rows=%lld / B=%lld out of range", (long long)n_rows, (long long)B);
-    NceLayout L;
-    nce_layout(n_rows, B, D, L);
-    return L.total;
+    return nce_carve(nullptr, n_rows, B, D).total;
 }
 
 int32_t wr_infonce_loss_grad(const float *A, const float *Bm, int64_t n_rows, int32_t D, const int64_t *idx, int64_t B, float tau,
@@ -357,54 +260,47 @@ int32_t wr_infonce_loss_grad(const float *A, const float *Bm, int64_t n_rows, in
     WR_REQUIRE((gA == nullptr) == (gB == nullptr), WR_E_NULL, "infonce: gA and gB go together (both NULL = loss only)");
     WR_REQUIRE(aligned16(A) && aligned16(Bm) && aligned16(gA) && aligned16(gB), WR_E_ALIGN, "infonce: tables must be 16-byte aligned");
     WR_REQUIRE(tau > 0.f && tau == tau && tau <= 3.0e38f, WR_E_RANGE, "infonce: tau must be positive and finite");
-    NceLayout L;
-    nce_layout(n_rows, B, D, L);
-    WR_REQUIRE(workspace && aligned16(workspace) && workspace_bytes >= L.total, WR_E_WORKSPACE, "infonce workspace %lld B < %lld B",
-               (long long)workspace_bytes, (long long)L.total);
+    const NceWs W = nce_carve(workspace, n_rows, B, D);
+    const int32_t rc = check_workspace("wr_infonce_loss_grad", workspace, workspace_bytes, W.total);
+    if (rc != WR_OK) return rc;
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    char *ws = reinterpret_cast<char *>(workspace);
-    float *Kn = reinterpret_cast<float *>(ws + L.Kn), *invB = reinterpret_cast<float *>(ws + L.invB);
-    int *owner = reinterpret_cast<int *>(ws + L.owner), *dup = reinterpret_cast<int *>(ws + L.dup);
-    float *Q = reinterpret_cast<float *>(ws + L.Q), *invA = reinterpret_cast<float *>(ws + L.invA);
-    int64_t *cidx = reinterpret_cast<int64_t *>(ws + L.cidx);
-    float *zpart = reinterpret_cast<float *>(ws + L.zpart), *part = reinterpret_cast<float *>(ws + L.part);
-    float *invZ = reinterpret_cast<float *>(ws + L.invZ), *lterm = reinterpret_cast<float *>(ws + L.lterm);
-    float *growA = reinterpret_cast<float *>(ws + L.growA), *growB = reinterpret_cast<float *>(ws + L.growB);
     const bool grad = gA != nullptr;
-    const int TS = nce_tile(D);
+    const int TS = pair_tile(D);
     const float inv_tau = 1.0f / tau, wtau = weight / tau, escale = 1.44269504088896341f / tau;
     const unsigned grid_n = (unsigned)((n_rows + kNceTeamsPerBlock - 1) / kNceTeamsPerBlock);
     const unsigned grid_b = (unsigned)((B + kNceTeamsPerBlock - 1) / kNceTeamsPerBlock);
 
-    hipLaunchKernelGGL(nce_prep_k_kernel, dim3(grid_n), dim3(kBlock), 0, stream, Bm, n_rows, D, Kn, invB, owner);
+    hipLaunchKernelGGL(nce_prep_k_kernel, dim3(grid_n), dim3(kBlock), 0, stream, Bm, n_rows, D, W.Kn, W.invB, W.owner);
     WR_LAUNCH_CHECK("nce_prep_k_kernel");
-    hipLaunchKernelGGL(nce_prep_q_kernel, dim3(grid_b), dim3(kBlock), 0, stream, A, n_rows, D, idx, B, Q, invA, cidx, owner, dup,
-                       err_word);
+    hipLaunchKernelGGL(nce_prep_q_kernel, dim3(grid_b), dim3(kBlock), 0, stream, A, n_rows, D, idx, B, W.Q, W.invA, W.cidx, W.owner,
+                       W.dup, err_word);
     WR_LAUNCH_CHECK("nce_prep_q_kernel");
     int64_t chunks, chunk_rows;
-    nce_chunks(B, n_rows, TS, chunks, chunk_rows);
+    pair_chunks(B, n_rows, TS, kNceTargetWg, chunks, chunk_rows);
     {
-        const dim3 grid((unsigned)((B + kNceRows - 1) / kNceRows), (unsigned)chunks);
-        if (grad) nce_launch_pass<true>(D, grid, stream, Q, B, Kn, n_rows, nullptr, escale, chunk_rows, part, zpart);
-        else nce_launch_pass<false>(D, grid, stream, Q, B, Kn, n_rows, nullptr, escale, chunk_rows, part, zpart);
+        const dim3 grid((unsigned)((B + kPairRows - 1) / kPairRows), (unsigned)chunks);
+        if (grad) nce_launch_pass<true>(D, grid, stream, W.Q, B, W.Kn, n_rows, nullptr, escale, chunk_rows, W.part, W.zpart);
+        else nce_launch_pass<false>(D, grid, stream, W.Q, B, W.Kn, n_rows, nullptr, escale, chunk_rows, W.part, W.zpart);
         WR_LAUNCH_CHECK("nce_pass_kernel (queries)");
     }
-    hipLaunchKernelGGL(nce_reduce_q_kernel, dim3(grid_b), dim3(kBlock), 0, stream, B, D, chunks, zpart, part, Q, invA, Kn, invB, cidx,
-                       owner, dup, wtau, inv_tau, invZ, lterm, growA, growB, grad ? 1 : 0);
+    hipLaunchKernelGGL(nce_reduce_q_kernel, dim3(grid_b), dim3(kBlock), 0, stream, B, D, chunks, W.zpart, W.part, W.Q, W.invA, W.Kn,
+                       W.invB, W.cidx, W.owner, W.dup, wtau, inv_tau, W.invZ, W.lterm, W.growA, W.growB, grad ? 1 : 0);
     WR_LAUNCH_CHECK("nce_reduce_q_kernel");
-    hipLaunchKernelGGL(nce_loss_kernel, dim3(1), dim3(kBlock), 0, stream, lterm, B, weight, accumulate, loss);
-    WR_LAUNCH_CHECK("nce_loss_kernel");
+    hipLaunchKernelGGL(pair_loss_kernel, dim3(1), dim3(kBlock), 0, stream, W.lterm, B, weight, accumulate, loss);
+    WR_LAUNCH_CHECK("pair_loss_kernel");
     if (!grad) return WR_OK;
-    nce_chunks(n_rows, B, TS, chunks, chunk_rows);
+    pair_chunks(n_rows, B, TS, kNceTargetWg, chunks, chunk_rows);
     {
-        const dim3 grid((unsigned)((n_rows + kNceRows - 1) / kNceRows), (unsigned)chunks);
-        nce_launch_pass<true>(D, grid, stream, Kn, n_rows, Q, B, invZ, escale, chunk_rows, part, nullptr);
+        const dim3 grid((unsigned)((n_rows + kPairRows - 1) / kPairRows), (unsigned)chunks);
+        nce_launch_pass<true>(D, grid, stream, W.Kn, n_rows, W.Q, B, W.invZ, escale, chunk_rows, W.part, nullptr);
         WR_LAUNCH_CHECK("nce_pass_kernel (items)");
     }
-    hipLaunchKernelGGL(nce_reduce_k_kernel, dim3(grid_n), dim3(kBlock), 0, stream, n_rows, D, chunks, part, Kn, invB, wtau, gB);
-    WR_LAUNCH_CHECK("nce_reduce_k_kernel");
+    // per row of Bm: sum_b softmax_bj q_b, scaled by weight / tau, back through the normalisation of Bm[j]
+    hipLaunchKernelGGL(pair_grad_kernel, dim3(grid_n), dim3(kBlock), 0, stream, n_rows, D, chunks, W.part, W.Kn, W.invB, wtau, gB);
+    WR_LAUNCH_CHECK("pair_grad_kernel (items)");
     WR_HIP(hipMemsetAsync(gA, 0, (size_t)n_rows * D * 4, stream));
-    hipLaunchKernelGGL(nce_scatter_kernel, dim3(grid_b), dim3(kBlock), 0, stream, B, D, cidx, owner, dup, growA, growB, gA, gB);
+    hipLaunchKernelGGL(nce_scatter_kernel, dim3(grid_b), dim3(kBlock), 0, stream, B, D, W.cidx, W.owner, W.dup, W.growA, W.growB, gA,
+                       gB);
     WR_LAUNCH_CHECK("nce_scatter_kernel");
     return WR_OK;
 }

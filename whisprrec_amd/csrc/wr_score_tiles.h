@@ -1,4 +1,6 @@
-// wr_score_tiles.h — the score-tile scan shared by wr_eval.hip, wr_topk.hip and wr_infonce.hip.
+// wr_score_tiles.h — the score tiles on the matrix cores.  The two scans: wr_eval.hip and wr_topk.hip.  TileStager, score_tiles
+// and acc_row without a scan: the streamed pair pass of wr_pair_pass.h (wr_infonce.hip, wr_supcon.hip).  The tile layout
+// (f32x16, acc_row) and WR_DISPATCH_KS alone: wr_buir.hip.
 //
 // scores = rows x items^T on the matrix cores: v_mfma_f32_32x32x2_f32 (f32 in, f32 accumulate = a k-ordered fmaf chain
 // started at 0, MI355X_MICROARCH.md "Matrix cores"), one 32x32 tile per wave and 32-item column block.  A workgroup =

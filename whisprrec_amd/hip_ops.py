@@ -98,6 +98,42 @@ def workspace(device, tag):
     return _WS[key]
 
 
+_SHAPE_WS = {}          # (tag, device, stream, shape) -> slot: nothing is allocated after the first call of a shape
+
+
+def _shape_workspace(tag, dev, shape, nbytes, err_word=False):
+    """the workspace of nbytes(*shape) bytes allocated at the first call of `shape` on this device and stream (the fused losses);
+    err_word: a zeroed int32 word is kept beside it -> (workspace, word)"""
+    key = (tag, str(dev), torch.cuda.current_stream(dev).cuda_stream, shape)
+    slot = _SHAPE_WS.get(key)
+    if slot is None:
+        slot = torch.empty(nbytes(*shape), dtype=torch.uint8, device=dev)
+        if err_word:
+            slot = (slot, torch.zeros(1, dtype=torch.int32, device=dev))
+        _SHAPE_WS[key] = slot
+    return slot
+
+
+def _release_shape_workspaces(tag):
+    for key in [k for k in _SHAPE_WS if k[0] == tag]:
+        del _SHAPE_WS[key]
+
+
+def _loss_slot(loss, dev):
+    """the `loss=` argument of the fused losses -> (the (1,) tensor the kernel writes, accumulate into it or overwrite)"""
+    if loss is None:
+        return torch.empty(1, dtype=torch.float32, device=dev), False
+    _req(loss, torch.float32, "loss")
+    if loss.numel() != 1:
+        raise ValueError("loss must hold one element")
+    return loss, True
+
+
+def _check_tau(tau):
+    if not (float(tau) > 0.0):
+        raise ValueError("tau must be positive (got %r)" % (tau,))
+
+
 def side_stream(device):
     """A stream for work that must OVERLAP the step kernels (plan builds, ring transfers).  HIP spreads the streams of
     one priority round-robin over a few hardware queues, and two streams that land on the same queue run one after the
@@ -1131,6 +1167,23 @@ def topk_supports(D, k):
     return bool(abi.lib().wr_topk_supported(int(D), int(k)))
 
 
+def _topk_blocks(n, n_items, D, k, dev):
+    """(lo, hi, workspace) for n rows in blocks whose workspace stays under TOPK_WORKSPACE_CAP (the bound never decreases in
+    the row count: halve until it fits)"""
+    L = abi.lib()
+
+    def nbytes(rows):
+        return abi.check_size(L.wr_topk_workspace_bytes(rows, n_items, D, k), "wr_topk_workspace_bytes")
+
+    block = max(n, 1)
+    while block > 128 and nbytes(block) > TOPK_WORKSPACE_CAP:
+        block = (block + 1) // 2
+    ws = workspace(dev, "topk")
+    for lo in range(0, n, block):
+        hi = min(n, lo + block)
+        yield lo, hi, ws.get(nbytes(hi - lo))
+
+
 def topk_recommend(user_mat, item_tab, users, k, mask_ptr=None, mask_idx=None):
     """The k unmasked items with the largest <user_mat[u], item_tab[j]> for every u in `users`, by score descending, then
     item id ascending (wr_topk_recommend).  Scores are bitwise those rank_eval computes.  Rows with fewer than k unmasked
@@ -1153,16 +1206,7 @@ def topk_recommend(user_mat, item_tab, users, k, mask_ptr=None, mask_idx=None):
     n, n_items = qu.numel(), item_tab.shape[0]
     items = torch.empty((n, k), dtype=torch.int32, device=dev)
     scores = torch.empty((n, k), dtype=torch.float32, device=dev)
-    # users in blocks whose workspace stays under the cap (the bound never decreases in n: halve until it fits)
-    block = max(n, 1)
-    while block > 128 and abi.check_size(L.wr_topk_workspace_bytes(block, n_items, D, k), "wr_topk_workspace_bytes") \
-            > TOPK_WORKSPACE_CAP:
-        block = (block + 1) // 2
-    ws = workspace(dev, "topk")
-    for lo in range(0, n, block):
-        hi = min(n, lo + block)
-        nb = abi.check_size(L.wr_topk_workspace_bytes(hi - lo, n_items, D, k), "wr_topk_workspace_bytes")
-        buf = ws.get(nb)
+    for lo, hi, buf in _topk_blocks(n, n_items, D, k, dev):
         abi.check(L.wr_topk_recommend(_p(user_mat), user_mat.shape[0], _p(item_tab), n_items, D, _p(qu[lo:hi]), hi - lo,
                                       _p(mask_ptr), _p(mask_idx), k, _p(items[lo:hi]), _p(scores[lo:hi]), _p(buf),
                                       buf.numel(), _stream()),
@@ -1228,16 +1272,7 @@ def topk_recommend_rows(query_mat, item_tab, k, mask_row=None, mask_ptr=None, ma
     n_mask_rows = 0 if mask_ptr is None else mask_ptr.numel() - 1
     items = torch.empty((n, k), dtype=torch.int32, device=dev)
     scores = torch.empty((n, k), dtype=torch.float32, device=dev)
-    # rows in blocks whose workspace stays under the cap, as topk_recommend blocks its users
-    block = max(n, 1)
-    while block > 128 and abi.check_size(L.wr_topk_workspace_bytes(block, n_items, D, k), "wr_topk_workspace_bytes") \
-            > TOPK_WORKSPACE_CAP:
-        block = (block + 1) // 2
-    ws = workspace(dev, "topk")
-    for lo in range(0, n, block):
-        hi = min(n, lo + block)
-        nb = abi.check_size(L.wr_topk_workspace_bytes(hi - lo, n_items, D, k), "wr_topk_workspace_bytes")
-        buf = ws.get(nb)
+    for lo, hi, buf in _topk_blocks(n, n_items, D, k, dev):
         # without query_row a block's queries are the rows lo.. of query_mat: the table pointer moves with the block
         qmat, q_rows = (query_mat, query_mat.shape[0]) if qr is not None else (query_mat[lo:hi], hi - lo)
         abi.check(L.wr_topk_recommend_rows(_p(qmat), q_rows, _p(item_tab), n_items, D, _p(qr[lo:hi]) if qr is not None else None,
@@ -1249,9 +1284,6 @@ def topk_recommend_rows(query_mat, item_tab, k, mask_row=None, mask_ptr=None, ma
 
 
 # ----------------------------------------------------------------------------------------------- InfoNCE (SGL)
-_INFONCE_WS = {}        # (device, stream, n, B, D) -> (workspace bytes, error word): nothing is allocated after the first call
-
-
 def infonce_supports(D):
     """embedding sizes wr_infonce_loss_grad takes (wr_infonce_supported)"""
     return bool(abi.lib().wr_infonce_supported(int(D)))
@@ -1277,16 +1309,9 @@ def infonce_loss_grad(A, Bm, idx, tau, weight=1.0, *, loss=None, grads=True, val
     B = ids.numel()
     if not infonce_supports(D):
         raise abi.WhisprRecHipError("infonce_loss_grad does not support D=%d (D in {32, 64, 128})" % D)
-    if not (float(tau) > 0.0):
-        raise ValueError("tau must be positive (got %r)" % (tau,))
+    _check_tau(tau)
     dev = A.device
-    accumulate = loss is not None
-    if accumulate:
-        _req(loss, torch.float32, "loss")
-        if loss.numel() != 1:
-            raise ValueError("loss must hold one element")
-    else:
-        loss = torch.empty(1, dtype=torch.float32, device=dev)
+    loss, accumulate = _loss_slot(loss, dev)
     gA = gB = None
     if grads:
         if out is not None:
@@ -1298,18 +1323,12 @@ def infonce_loss_grad(A, Bm, idx, tau, weight=1.0, *, loss=None, grads=True, val
         else:
             gA = torch.empty((n, D), dtype=torch.float32, device=dev)
             gB = torch.empty((n, D), dtype=torch.float32, device=dev)
-    L = abi.lib()
-    key = (str(dev), torch.cuda.current_stream(dev).cuda_stream, n, B, D)
-    slot = _INFONCE_WS.get(key)
-    if slot is None:
-        nbytes = infonce_workspace_bytes(n, B, D)
-        slot = (torch.empty(nbytes, dtype=torch.uint8, device=dev), torch.zeros(1, dtype=torch.int32, device=dev))
-        _INFONCE_WS[key] = slot
-    ws, err = slot
+    ws, err = _shape_workspace("infonce", dev, (n, B, D), infonce_workspace_bytes, err_word=True)
     if validate:
         err.zero_()
-    abi.check(L.wr_infonce_loss_grad(_p(A), _p(Bm), n, D, _p(ids), B, float(tau), float(weight), _p(loss), int(accumulate),
-                                     _p(gA), _p(gB), _p(err) if validate else None, _p(ws), ws.numel(), _stream()),
+    abi.check(abi.lib().wr_infonce_loss_grad(_p(A), _p(Bm), n, D, _p(ids), B, float(tau), float(weight), _p(loss),
+                                             int(accumulate), _p(gA), _p(gB), _p(err) if validate else None, _p(ws), ws.numel(),
+                                             _stream()),
               "wr_infonce_loss_grad")
     if validate and int(err.item()) != 0:
         raise IndexError("infonce_loss_grad: idx holds an id outside [0, %d)" % n)
@@ -1318,7 +1337,7 @@ def infonce_loss_grad(A, Bm, idx, tau, weight=1.0, *, loss=None, grads=True, val
 
 def infonce_release_workspaces():
     """drop the cached workspaces (they are as large as a table at big n)"""
-    _INFONCE_WS.clear()
+    _release_shape_workspaces("infonce")
 
 
 # ----------------------------------------------------------------------------------------------- SASRec block (K13)
@@ -1426,9 +1445,6 @@ def sasrec_block(x, block_module, n_heads, p, seed, training, key_lengths=None, 
 
 
 # ----------------------------------------------------------------------------------------------- supervised contrastive loss (K15)
-_SUPCON_WS = {}         # (device, stream, B, D) -> workspace: nothing is allocated after the first call of a shape
-
-
 def supcon_supports(D):
     """embedding sizes wr_supcon_loss_grad takes (wr_supcon_supported)"""
     return bool(abi.lib().wr_supcon_supported(int(D)))
@@ -1455,28 +1471,19 @@ def supcon_loss_grad(F, labels, tau, weight=1.0, *, loss=None, grads=True):
     if not supcon_supports(D) or B < 1 or N > SUPCON_MAX_ROWS:
         raise abi.WhisprRecHipError("supcon_loss_grad does not support D=%d, B=%d (D in {32, 64, 128}, 1 <= B, 2 B <= %d)"
                                     % (D, B, SUPCON_MAX_ROWS))
-    if not (float(tau) > 0.0):
-        raise ValueError("tau must be positive (got %r)" % (tau,))
+    _check_tau(tau)
     dev = F.device
-    accumulate = loss is not None
-    if accumulate:
-        _req(loss, torch.float32, "loss")
-        if loss.numel() != 1:
-            raise ValueError("loss must hold one element")
-    else:
-        loss = torch.empty(1, dtype=torch.float32, device=dev)
+    loss, accumulate = _loss_slot(loss, dev)
     gF = torch.empty((N, D), dtype=torch.float32, device=dev) if grads else None
-    key = (str(dev), torch.cuda.current_stream(dev).cuda_stream, B, D)
-    ws = _SUPCON_WS.get(key)
-    if ws is None:
-        ws = _SUPCON_WS[key] = torch.empty(supcon_workspace_bytes(B, D), dtype=torch.uint8, device=dev)
+    ws = _shape_workspace("supcon", dev, (B, D), supcon_workspace_bytes)
     abi.check(abi.lib().wr_supcon_loss_grad(_p(F), B, D, _p(lab), float(tau), _p(loss), int(accumulate), float(weight), _p(gF), None,
                                             _p(ws), ws.numel(), _stream()), "wr_supcon_loss_grad")
     return loss, gF
 
 
 def supcon_release_workspaces():
-    _SUPCON_WS.clear()
+    """drop the cached workspaces"""
+    _release_shape_workspaces("supcon")
 
 
 class _SupCon(torch.autograd.Function):
@@ -1500,9 +1507,6 @@ def supcon_loss(F, labels, tau):
 
 
 # ----------------------------------------------------------------------------------------------- BUIR (K16, K17)
-_BUIR_WS = {}           # (device, stream, B, D) -> workspace: nothing is allocated after the first call of a shape
-
-
 def buir_supports(D):
     """embedding sizes wr_buir_loss_grad takes (wr_buir_supported)"""
     return bool(abi.lib().wr_buir_supported(int(D)))
@@ -1545,15 +1549,17 @@ def buir_loss_grad(user_online_w, item_online_w, user_target_w, item_target_w, W
         gI = torch.empty((B, D), dtype=torch.float32, device=dev)
         gW = torch.empty((D, D), dtype=torch.float32, device=dev)
         gb = torch.empty(D, dtype=torch.float32, device=dev)
-    key = (str(dev), torch.cuda.current_stream(dev).cuda_stream, B, D)
-    ws = _BUIR_WS.get(key)
-    if ws is None:
-        ws = _BUIR_WS[key] = torch.empty(buir_workspace_bytes(B, D), dtype=torch.uint8, device=dev)
+    ws = _shape_workspace("buir", dev, (B, D), buir_workspace_bytes)
     abi.check(abi.lib().wr_buir_loss_grad(_p(user_online_w), _p(item_online_w), _p(user_target_w), _p(item_target_w),
                                           user_online_w.shape[0], item_online_w.shape[0], D, _p(W), _p(b), _p(uu), _p(ii), B, _p(loss),
                                           _p(gU), _p(gI), _p(gW), _p(gb), _p(err_word), _p(ws), ws.numel(), _stream()),
               "wr_buir_loss_grad")
     return loss, gU, gI, gW, gb
+
+
+def buir_release_workspaces():
+    """drop the cached workspaces"""
+    _release_shape_workspaces("buir")
 
 
 class _BuirLoss(torch.autograd.Function):
