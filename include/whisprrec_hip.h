@@ -946,6 +946,57 @@ int32_t wr_buir_loss_grad(const float *user_online, const float *item_online, co
  *      rewritten (t m + t (1 - m) is not t in fp32).  t and o 16-byte aligned, n >= 1. */
 int32_t wr_ema_update(float *t, const float *o, int64_t n, float m, float one_minus_m, void *stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * K18  IF4Rec's interest pooling (src/models/sequential/IF4Rec.py:87-103), forward and backward, without the [B, T, D] gather
+ *      or the [B, K, T, D] product in global memory.  item_tab [n_items, D], pos_tab [n_pos_rows, D] or NULL (add_pos 0),
+ *      history int64 [B, T], W1 [A, D], b1 [A], W2 [K, A], b2 [K] (nn.Linear: out x in), all fp32 row-major:
+ *   valid[t] = history[b][t] > 0              hp[t] = item_tab[history[b][t]] + pos_tab[t]
+ *   s[k][t]  = b2[k] + <W2[k], leaky_relu(W1 hp[t] + b1, 0.01)> for valid t, -inf otherwise
+ *   p[k][.]  = softmax_t s[k][.]   (a row with no valid entry: all 0, the reference's NaN rule)
+ *   out[b][k] = sum_t p[k][t] hp[t]                                                                    out [B, K, D]
+ *   - Supported (wr_interest_pool_supported): D in {32, 64, 128}, 1 <= A <= 32, 1 <= K <= 8, 1 <= T <= 64, 1 <= B <= 2^24;
+ *     n_pos_rows >= T.  Anything else, a NULL or misaligned (16 B) table or a short workspace is refused before any launch.
+ *   - The softmax subtracts each row's own maximum, not the reference's maximum over the whole call: softmax is invariant under
+ *     the shift, the results differ by the rounding of s - max only (wr_if4rec.hip, file header).
+ *   - wr_interest_pool_fwd: one launch.  A sequence's valid rows are gathered once into LDS; padded positions are not read.
+ *   - wr_interest_pool_bwd: g_out [B, K, D] -> g_hp [B, T, D] (gradient w.r.t. item row + position row, exactly 0 at masked
+ *     positions; scatter-add it for the item-table gradient), gW1 [A, D], gb1 [A], gW2 [K, A], gb2 [K] and gpos [n_pos_rows, D]
+ *     (NULL iff pos_tab is NULL; rows at or past T are written as zeros), all fully written.  The forward is recomputed from
+ *     the ids.  Workgroup w accumulates the parameter gradients of sequences w, w + G, ... (G = min(B, 512)) in registers and
+ *     writes one row of partials; a second launch folds the rows in workgroup order.  No float atomics: same inputs, same
+ *     bits.  A row zeroed by the NaN rule passes no gradient (autograd would pass NaN), the deviation K13 documents.
+ *   - An id outside [0, n_items) is clamped into the table before it addresses anything and ORs 1 into err_word (int32 on the
+ *     device, may be NULL; the caller clears and reads it).
+ *   - workspace >= wr_interest_pool_workspace_bytes(B, D, A, K, T), 16-byte aligned (backward only).  No host round trip, no
+ *     allocation. */
+int32_t wr_interest_pool_supported(int32_t D, int32_t A, int32_t K, int32_t T);
+int64_t wr_interest_pool_workspace_bytes(int64_t B, int32_t D, int32_t A, int32_t K, int32_t T);
+int32_t wr_interest_pool_fwd(const float *item_tab, int64_t n_items, const float *pos_tab, int64_t n_pos_rows, int32_t D,
+                             const int64_t *history, int64_t B, int32_t T, const float *W1, const float *b1, const float *W2,
+                             const float *b2, int32_t A, int32_t K, float *out, int32_t *err_word, void *stream);
+int32_t wr_interest_pool_bwd(const float *item_tab, int64_t n_items, const float *pos_tab, int64_t n_pos_rows, int32_t D,
+                             const int64_t *history, int64_t B, int32_t T, const float *W1, const float *b1, const float *W2,
+                             const float *b2, int32_t A, int32_t K, const float *g_out, float *g_hp, float *gW1, float *gb1,
+                             float *gW2, float *gb2, float *gpos, int32_t *err_word, void *workspace, int64_t workspace_bytes,
+                             void *stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * K19  Ranking evaluation with KQ query vectors per row — multi-interest models (IF4Rec.py:117-118):
+ *   score(e, j)     = max_{k < KQ} <query_mat[e KQ + k], item_tab[j]>                        query_mat [n KQ, D]
+ *   rank[e]         = 1 + #{ j not masked for e : score(e, j) > target_score[e] },   target_score[e] = score(e, eval_target[e])
+ *   - The scans of K10 / K14 run unchanged over the n KQ query rows; a consumer takes the maximum of the KQ adjacent accumulator
+ *     registers that hold one row's interests and counts once per row.  Each <.,.> is the fp32 k-ordered chain of
+ *     v_mfma_f32_32x32x2_f32, target_score is the maximum of the same chains: the target's own column never counts.
+ *   - mask_row int64 [n KQ]: the mask list of QUERY row r = e KQ + k, i.e. row e's entry repeated KQ times (the caller repeats
+ *     it on the device); mask_row, mask_ptr and mask_idx are all NULL or all non-NULL.  Ids are trusted as in K14.
+ *   - KQ in {1, 2, 4} and the D of wr_rank_eval (wr_rank_eval_multi_supported); KQ = 8 would cross the half-wave.  With KQ = 1
+ *     every output is bitwise that of wr_rank_eval_rows without query_row.  wr_rank_eval / wr_rank_eval_rows do not change.
+ *   - Argument errors (WR_E_*) are reported before anything is launched. */
+int32_t wr_rank_eval_multi_supported(int32_t D, int32_t KQ);
+int32_t wr_rank_eval_multi(const float *query_mat, int64_t n_query_rows, const float *item_tab, int64_t n_items, int32_t D,
+                           int32_t KQ, const int64_t *eval_target, int64_t n, const int64_t *mask_row, int64_t n_mask_rows,
+                           const int64_t *mask_ptr, const int32_t *mask_idx, int32_t *rank, float *target_score, void *stream);
+
 /* LightGCN.predict's per-batch tail in two launches (src/models/general/LightGCN.py:156-175, src/utils/loss.py:37-39,94-98):
  *   loss[0] = mean_b( -log(1e-10 + sigmoid(<Ua[u_b], Ia[p_b]> - <Ua[u_b], Ia[n_b]>)) )
  *             + reg_weight * (||U0[u]||_F + ||I0[p]||_F + ||I0[n]||_F) / B

@@ -199,6 +199,14 @@ SIGNATURES = {
     "wr_buir_loss_grad": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp,
                                   c_vp, c_vp, c_vp, c_i64, c_vp]),
     "wr_ema_update": (c_i32, [c_vp, c_vp, c_i64, c_f32, c_f32, c_vp]),
+    "wr_interest_pool_supported": (c_i32, [c_i32, c_i32, c_i32, c_i32]),
+    "wr_interest_pool_workspace_bytes": (c_i64, [c_i64, c_i32, c_i32, c_i32, c_i32]),
+    "wr_interest_pool_fwd": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i32, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp,
+                                     c_vp, c_vp]),
+    "wr_interest_pool_bwd": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i32, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp,
+                                     c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "wr_rank_eval_multi_supported": (c_i32, [c_i32, c_i32]),
+    "wr_rank_eval_multi": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i32, c_i32, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "wr_lightgcn_loss_workspace_bytes": (c_i64, [c_i64]),
     "wr_lightgcn_loss": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_vp, c_vp, c_vp, c_i64, c_f32, c_vp, c_vp, c_vp,
                                  c_i64, c_vp]),

@@ -142,6 +142,148 @@ static int32_t rank_eval_launch(const float *query_mat, const float *item_tab, i
     return WR_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ K19: KQ queries per row
+// A multi-interest model (IF4Rec) scores row e against item j with max_k <Q[e KQ + k], I[j]>.  The scans run unchanged over
+// the n KQ query rows (query row e KQ + k = interest k of row e, its mask row repeated KQ times); only the consumer differs:
+// acc_row(reg, half) = (reg & 3) + 8 (reg >> 2) + 4 half puts the KQ in {1, 2, 4} query rows of one evaluation row into KQ
+// ADJACENT accumulator registers of one lane, so their maximum is taken in registers, compared with the row's target score
+// and counted once.  128 rows per workgroup and 32 per wave are multiples of KQ: no group straddles a slab.
+
+// target score = max over k of the k-ordered fmaf chain the MFMA accumulates: the target's own column equals it exactly
+template <int KQ>
+__global__ __launch_bounds__(kBlock) void eval_target_multi_kernel(const float *__restrict__ Q, const float *__restrict__ I, int D,
+                                                                    const int64_t *__restrict__ et, int64_t n,
+                                                                    float *__restrict__ tscore) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const float *b = I + et[i] * (int64_t)D;
+    float best = 0.f;
+#pragma unroll
+    for (int q = 0; q < KQ; ++q) {
+        const float *a = Q + (i * KQ + q) * (int64_t)D;
+        float s = 0.f;
+        for (int k = 0; k < D; ++k) s = fmaf(a[k], b[k], s);
+        best = q == 0 ? s : fmaxf(best, s);
+    }
+    tscore[i] = best;
+}
+
+template <int KQ>
+struct RankCountMulti {
+    static constexpr int NG = 16 / KQ;     // evaluation rows per lane
+    float trow[NG];
+    int cnt[NG];
+    int64_t q_first, n, n_items;           // first QUERY row of the slab; n evaluation rows
+    int col, half;
+
+    __device__ __forceinline__ RankCountMulti(const float *__restrict__ tscore, int64_t n_, int64_t n_items_)
+        : q_first((int64_t)blockIdx.x * kScoreRows + (threadIdx.x >> 6) * 32), n(n_), n_items(n_items_),
+          col(threadIdx.x & 31), half((threadIdx.x & 63) >> 5) {
+#pragma unroll
+        for (int g = 0; g < NG; ++g) {
+            const int64_t e = (q_first + acc_row(g * KQ, half)) / KQ;
+            trow[g] = (e < n) ? tscore[e] : 3.4e38f;   // rows past the end never count
+            cnt[g] = 0;
+        }
+    }
+
+    template <int C>
+    __device__ __forceinline__ float best(const f32x16 (&acc)[C], int c, int g) const {
+        float m = acc[c][g * KQ];
+#pragma unroll
+        for (int q = 1; q < KQ; ++q) m = fmaxf(m, acc[c][g * KQ + q]);
+        return m;
+    }
+
+    template <int C, typename Masked>
+    __device__ __forceinline__ void operator()(const f32x16 (&acc)[C], int64_t j0, bool plain, Masked masked) {
+        if (plain) {
+#pragma unroll
+            for (int g = 0; g < NG; ++g) {
+#pragma unroll
+                for (int c = 0; c < C; ++c) cnt[g] += best<C>(acc, c, g) > trow[g] ? 1 : 0;
+            }
+        } else {
+#pragma unroll
+            for (int g = 0; g < NG; ++g) {
+                const int row = acc_row(g * KQ, half);      // the KQ query rows of a group share one mask list
+#pragma unroll
+                for (int c = 0; c < C; ++c) {
+                    const bool ok = j0 + c * 32 + col < n_items;
+                    const bool m = masked(c, row);
+                    cnt[g] += (ok && !m && best<C>(acc, c, g) > trow[g]) ? 1 : 0;
+                }
+            }
+        }
+    }
+
+    __device__ __forceinline__ void flush(int *__restrict__ rank_cnt) const {
+#pragma unroll
+        for (int g = 0; g < NG; ++g) {
+            int v = cnt[g];
+            v += __shfl_xor(v, 1, 64); v += __shfl_xor(v, 2, 64); v += __shfl_xor(v, 4, 64);
+            v += __shfl_xor(v, 8, 64); v += __shfl_xor(v, 16, 64);
+            const int64_t e = (q_first + acc_row(g * KQ, half)) / KQ;
+            if (col == 0 && e < n && v) atomicAdd(&rank_cnt[e], v);
+        }
+    }
+};
+
+template <int KQ>
+__global__ __launch_bounds__(kBlock) void eval_rank_multi_kernel(const float *__restrict__ Q, const float *__restrict__ I, int D,
+                                                                  int64_t n_items, const int64_t *__restrict__ mrows,
+                                                                  const float *__restrict__ tscore, int64_t n,
+                                                                  const int64_t *__restrict__ mask_ptr, const int *__restrict__ mask_idx,
+                                                                  int *__restrict__ rank_cnt) {
+    RankCountMulti<KQ> count(tscore, n, n_items);
+    score_scan_lds(Q, I, D, n_items, nullptr, mrows, n * KQ, mask_ptr, mask_idx, (int64_t)blockIdx.y * kEvalChunk, kEvalChunk, count);
+    count.flush(rank_cnt);
+}
+
+template <int KS, int KQ>
+__global__ __launch_bounds__(kBlock, 3) void eval_rank_multi_kernel_rega(const float *__restrict__ Q, const float *__restrict__ I,
+                                                                       int64_t n_items, const int64_t *__restrict__ mrows,
+                                                                       const float *__restrict__ tscore, int64_t n,
+                                                                       const int64_t *__restrict__ mask_ptr,
+                                                                       const int *__restrict__ mask_idx, int *__restrict__ rank_cnt) {
+    RankCountMulti<KQ> count(tscore, n, n_items);
+    score_scan_rega<KS>(Q, I, n_items, nullptr, mrows, n * KQ, mask_ptr, mask_idx, (int64_t)blockIdx.y * kEvalChunk, kEvalChunk, count);
+    count.flush(rank_cnt);
+}
+
+template <int KQ>
+static int32_t rank_eval_multi_launch(const float *query_mat, const float *item_tab, int64_t n_items, int32_t D, const int64_t *mrows,
+                                      const int64_t *eval_target, int64_t n, const int64_t *mask_ptr, const int32_t *mask_idx,
+                                      int32_t *rank, float *target_score, hipStream_t stream) {
+    WR_HIP(hipMemsetAsync(rank, 0, (size_t)n * 4, stream));
+    hipLaunchKernelGGL(eval_target_multi_kernel<KQ>, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, query_mat,
+                       item_tab, D, eval_target, n, target_score);
+    WR_LAUNCH_CHECK("eval_target_multi_kernel");
+    const dim3 grid((unsigned)((n * KQ + kScoreRows - 1) / kScoreRows), (unsigned)((n_items + kEvalChunk - 1) / kEvalChunk));
+    if (score_rega_d(D)) {
+#define WR_EVAL_MULTI_REGA(KS_)                                                                                        \
+    hipLaunchKernelGGL((eval_rank_multi_kernel_rega<KS_, KQ>), grid, dim3(kBlock), 0, stream, query_mat, item_tab, n_items, mrows, \
+                       target_score, n, mask_ptr, mask_idx, rank)
+        WR_DISPATCH_KS(D, 4, 32, WR_EVAL_MULTI_REGA);
+#undef WR_EVAL_MULTI_REGA
+    } else {
+        const size_t lds = score_lds_bytes(D, 1);
+        if (lds > 64 * 1024)
+            WR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(eval_rank_multi_kernel<KQ>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(eval_rank_multi_kernel<KQ>, grid, dim3(kBlock), lds, stream, query_mat, item_tab, D, n_items, mrows,
+                           target_score, n, mask_ptr, mask_idx, rank);
+    }
+    WR_LAUNCH_CHECK("eval_rank_multi_kernel");
+    hipLaunchKernelGGL(eval_finish_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, rank, n);
+    WR_LAUNCH_CHECK("eval_finish_kernel");
+    return WR_OK;
+}
+
+static inline bool rank_eval_d_ok(int32_t D) {
+    return D >= 4 && D % 4 == 0 && (score_rega_d(D) || score_lds_bytes(D, 1) <= kLdsPerWorkgroup);
+}
+
 // D outside {8,16,32,64}: the LDS-operand kernel stages (128 + 32) rows of D + 1 floats + 128 bitmap words; a
 // workgroup gets at most 160 KiB (163,840 B) on gfx950 -> D <= 252
 #define WR_EVAL_REQUIRE_D(D_)                                                                                          \
@@ -189,6 +331,38 @@ int32_t wr_rank_eval_rows(const float *query_mat, int64_t n_query_rows, const fl
     if (n == 0) return WR_OK;
     return rank_eval_launch(query_mat, item_tab, n_items, D, query_row, mask_row, eval_target, n, mask_ptr, mask_idx, rank,
                             target_score, reinterpret_cast<hipStream_t>(stream_));
+}
+
+int32_t wr_rank_eval_multi_supported(int32_t D, int32_t KQ) {
+    return (rank_eval_d_ok(D) && (KQ == 1 || KQ == 2 || KQ == 4)) ? 1 : 0;
+}
+
+int32_t wr_rank_eval_multi(const float *query_mat, int64_t n_query_rows, const float *item_tab, int64_t n_items, int32_t D,
+                           int32_t KQ, const int64_t *eval_target, int64_t n, const int64_t *mask_row, int64_t n_mask_rows,
+                           const int64_t *mask_ptr, const int32_t *mask_idx, int32_t *rank, float *target_score, void *stream_) {
+    int32_t rc;
+    WR_REQUIRE(KQ == 1 || KQ == 2 || KQ == 4, WR_E_RANGE, "rank_eval_multi supports KQ in {1, 2, 4}; got KQ=%d", KQ);
+    if ((rc = check_table(query_mat, n_query_rows, D, "query_mat")) != WR_OK) return rc;
+    if ((rc = check_table(item_tab, n_items, D, "item_tab")) != WR_OK) return rc;
+    WR_REQUIRE(eval_target && rank && target_score, WR_E_NULL, "rank_eval_multi: NULL argument");
+    WR_REQUIRE((mask_ptr == nullptr) == (mask_idx == nullptr) && (mask_ptr == nullptr) == (mask_row == nullptr), WR_E_NULL,
+               "rank_eval_multi: mask_row, mask_ptr and mask_idx go together");
+    WR_REQUIRE(n >= 0 && n * KQ < (int64_t(1) << 31), WR_E_SHAPE, "rank_eval_multi: n out of range");
+    WR_REQUIRE(n * KQ <= n_query_rows, WR_E_SHAPE, "rank_eval_multi: n=%lld rows of %d queries but query_mat has %lld rows",
+               (long long)n, KQ, (long long)n_query_rows);
+    WR_REQUIRE(mask_ptr == nullptr || n_mask_rows >= 1, WR_E_SHAPE, "rank_eval_multi: n_mask_rows=%lld with a mask",
+               (long long)n_mask_rows);
+    WR_EVAL_REQUIRE_D(D);
+    if (n == 0) return WR_OK;
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    if (KQ == 1)
+        return rank_eval_multi_launch<1>(query_mat, item_tab, n_items, D, mask_row, eval_target, n, mask_ptr, mask_idx, rank,
+                                         target_score, stream);
+    if (KQ == 2)
+        return rank_eval_multi_launch<2>(query_mat, item_tab, n_items, D, mask_row, eval_target, n, mask_ptr, mask_idx, rank,
+                                         target_score, stream);
+    return rank_eval_multi_launch<4>(query_mat, item_tab, n_items, D, mask_row, eval_target, n, mask_ptr, mask_idx, rank,
+                                     target_score, stream);
 }
 
 }  // extern "C"

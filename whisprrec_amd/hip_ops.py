@@ -1258,6 +1258,40 @@ def rank_eval_rows(query_mat, item_tab, eval_target, mask_row=None, mask_ptr=Non
     return rank, tsc
 
 
+RANK_EVAL_MULTI_KQ = (1, 2, 4)
+
+
+def rank_eval_multi_supports(D, KQ):
+    """(embedding size, queries per row) wr_rank_eval_multi takes (wr_rank_eval_multi_supported): rank_eval's D, KQ in {1, 2, 4}"""
+    return bool(abi.lib().wr_rank_eval_multi_supported(int(D), int(KQ)))
+
+
+def rank_eval_multi(queries, item_tab, eval_target, mask_row=None, mask_ptr=None, mask_idx=None):
+    """rank_eval_rows for a model with KQ query vectors per row (wr_rank_eval_multi; IF4Rec's interests): queries [n, KQ, D],
+    the score of row e against item j is max_k <queries[e, k], item_tab[j]>, and row e is masked by the list of row mask_row[e]
+    of the CSR (repeated KQ times here, on the device: the scan sees n KQ query rows).  Returns (rank int32 [n], target_score
+    fp32 [n]); with KQ = 1 the bits of rank_eval_rows."""
+    _req(queries, torch.float32, "queries", 3)
+    n, KQ, D = (int(v) for v in queries.shape)
+    if not rank_eval_multi_supports(D, KQ):
+        raise abi.WhisprRecHipError("rank_eval_multi does not support D=%d with %d queries per row (D as for rank_eval, queries per "
+                                    "row in {1, 2, 4})" % (D, KQ))
+    qmat = queries.view(n * KQ, D)
+    if eval_target.numel() != n:
+        raise ValueError("rank_eval_multi: eval_target has %d entries for %d rows" % (eval_target.numel(), n))
+    _, _, mr = _rows_args("rank_eval_multi", qmat, item_tab, n, mask_row, mask_ptr, mask_idx, None)
+    et = _idx64(eval_target.reshape(-1), "eval_target")
+    if mr is not None:
+        mr = mr.repeat_interleave(KQ).contiguous()
+    rank = torch.empty(n, dtype=torch.int32, device=queries.device)
+    tsc = torch.empty(n, dtype=torch.float32, device=queries.device)
+    n_mask_rows = 0 if mask_ptr is None else mask_ptr.numel() - 1
+    abi.check(abi.lib().wr_rank_eval_multi(_p(qmat), n * KQ, _p(item_tab), item_tab.shape[0], D, KQ, _p(et), n, _p(mr), n_mask_rows,
+                                           _p(mask_ptr), _p(mask_idx), _p(rank), _p(tsc), _stream()),
+              "wr_rank_eval_multi")
+    return rank, tsc
+
+
 def topk_recommend_rows(query_mat, item_tab, k, mask_row=None, mask_ptr=None, mask_idx=None, query_row=None):
     """topk_recommend with one query vector per row (wr_topk_recommend_rows; the roles as in rank_eval_rows): n =
     len(query_row), or every row of query_mat.  Order, ties, padding and the bits of the scores are topk_recommend's.
@@ -1609,6 +1643,108 @@ def ema_update_(target, online, momentum):
 
 
 # ----------------------------------------------------------------------------------------------- optimizers
+# ----------------------------------------------------------------------------------------------- IF4Rec interest pooling (K18)
+def interest_pool_supports(D, A, K, T):
+    """shapes wr_interest_pool_fwd / _bwd take (wr_interest_pool_supported): D in {32, 64, 128}, A <= 32, K <= 8, T <= 64"""
+    return bool(abi.lib().wr_interest_pool_supported(int(D), int(A), int(K), int(T)))
+
+
+def interest_pool_workspace_bytes(B, D, A, K, T):
+    return abi.check_size(abi.lib().wr_interest_pool_workspace_bytes(int(B), int(D), int(A), int(K), int(T)),
+                          "wr_interest_pool_workspace_bytes")
+
+
+def _interest_pool_args(item_weight, pos_weight, history, W1, b1, W2, b2, err_word):
+    """the argument checks of interest_pool_fwd / _bwd -> (history int64 [B, T], B, T, D, A, K)"""
+    _req(item_weight, torch.float32, "item_weight", 2)
+    if pos_weight is not None:
+        _req(pos_weight, torch.float32, "pos_weight", 2)
+    _req(W1, torch.float32, "W1", 2)
+    _req(b1, torch.float32, "b1", 1)
+    _req(W2, torch.float32, "W2", 2)
+    _req(b2, torch.float32, "b2", 1)
+    if not isinstance(history, torch.Tensor) or history.dim() != 2:
+        raise ValueError("history must be a [B, T] tensor")
+    hist = _idx64(history, "history")
+    B, T = (int(v) for v in hist.shape)
+    D, A, K = int(item_weight.shape[1]), int(W1.shape[0]), int(W2.shape[0])
+    if tuple(W1.shape) != (A, D) or b1.numel() != A or tuple(W2.shape) != (K, A) or b2.numel() != K:
+        raise ValueError("W1 must be [A, D], b1 [A], W2 [K, A] and b2 [K] with D the embedding size of the item table (got %s, %s, "
+                         "%s, %s for D=%d)" % (tuple(W1.shape), tuple(b1.shape), tuple(W2.shape), tuple(b2.shape), D))
+    if pos_weight is not None and (pos_weight.shape[1] != D or pos_weight.shape[0] < T):
+        raise ValueError("pos_weight must hold at least T=%d rows of D=%d (got %s)" % (T, D, tuple(pos_weight.shape)))
+    if B < 1 or not interest_pool_supports(D, A, K, T):
+        raise abi.WhisprRecHipError("interest_pool does not support B=%d D=%d A=%d K=%d T=%d (D in {32, 64, 128}, 1 <= A <= 32, "
+                                    "1 <= K <= 8, 1 <= T <= 64, B >= 1)" % (B, D, A, K, T))
+    if err_word is not None:
+        _req(err_word, torch.int32, "err_word")
+    return hist, B, T, D, A, K
+
+
+def interest_pool_fwd(item_weight, pos_weight, history, W1, b1, W2, b2, err_word=None):
+    """IF4Rec's interest vectors [B, K, D] (IF4Rec.py:87-103) in one launch of wr_interest_pool_fwd: no [B, T, D] gather, no
+    [B, K, T, D] product.  pos_weight None: add_pos 0.  An id outside the item table is clamped and ORs 1 into `err_word` (an
+    int32 (1,) device tensor the caller clears and reads, or None)."""
+    hist, B, T, D, A, K = _interest_pool_args(item_weight, pos_weight, history, W1, b1, W2, b2, err_word)
+    out = torch.empty((B, K, D), dtype=torch.float32, device=item_weight.device)
+    n_pos = 0 if pos_weight is None else pos_weight.shape[0]
+    abi.check(abi.lib().wr_interest_pool_fwd(_p(item_weight), item_weight.shape[0], _p(pos_weight), n_pos, D, _p(hist), B, T, _p(W1),
+                                             _p(b1), _p(W2), _p(b2), A, K, _p(out), _p(err_word), _stream()), "wr_interest_pool_fwd")
+    return out
+
+
+def interest_pool_bwd(item_weight, pos_weight, history, W1, b1, W2, b2, g_out, err_word=None):
+    """The gradients of interest_pool_fwd for g_out [B, K, D] (wr_interest_pool_bwd; the forward is recomputed from the ids):
+    (g_hp [B, T, D], gW1, gb1, gW2, gb2, gpos or None).  g_hp is the gradient w.r.t. item row + position row, exactly 0 at
+    masked positions; gpos has the shape of pos_weight.  No float atomics: same inputs, same bits."""
+    hist, B, T, D, A, K = _interest_pool_args(item_weight, pos_weight, history, W1, b1, W2, b2, err_word)
+    _req(g_out, torch.float32, "g_out", 3)
+    if tuple(g_out.shape) != (B, K, D):
+        raise ValueError("g_out must be [B, K, D] = %s (got %s)" % ((B, K, D), tuple(g_out.shape)))
+    dev = item_weight.device
+    g_hp = torch.empty((B, T, D), dtype=torch.float32, device=dev)
+    gW1, gb1, gW2, gb2 = (torch.empty_like(t) for t in (W1, b1, W2, b2))
+    gpos = None if pos_weight is None else torch.empty_like(pos_weight)
+    n_pos = 0 if pos_weight is None else pos_weight.shape[0]
+    ws = workspace(dev, "interest_pool").get(interest_pool_workspace_bytes(B, D, A, K, T))
+    abi.check(abi.lib().wr_interest_pool_bwd(_p(item_weight), item_weight.shape[0], _p(pos_weight), n_pos, D, _p(hist), B, T, _p(W1),
+                                             _p(b1), _p(W2), _p(b2), A, K, _p(g_out), _p(g_hp), _p(gW1), _p(gb1), _p(gW2), _p(gb2),
+                                             _p(gpos), _p(err_word), _p(ws), ws.numel(), _stream()), "wr_interest_pool_bwd")
+    return g_hp, gW1, gb1, gW2, gb2, gpos
+
+
+class _InterestPool(torch.autograd.Function):
+    """wr_interest_pool_fwd / _bwd: saves the ids and the parameters, no activation"""
+
+    @staticmethod
+    def forward(ctx, item_weight, pos_weight, W1, b1, W2, b2, history, err_word):
+        args = [t.detach() if t is not None else None for t in (item_weight, pos_weight, W1, b1, W2, b2)]
+        out = interest_pool_fwd(args[0], args[1], history, *args[2:], err_word=err_word)
+        ctx.has_pos = pos_weight is not None
+        ctx.save_for_backward(history, *[t for t in args if t is not None])
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        history, item_weight = ctx.saved_tensors[:2]
+        rest = list(ctx.saved_tensors[2:])
+        pos_weight = rest.pop(0) if ctx.has_pos else None
+        W1, b1, W2, b2 = rest
+        g_hp, gW1, gb1, gW2, gb2, gpos = interest_pool_bwd(item_weight, pos_weight, history, W1, b1, W2, b2, grad_out.contiguous())
+        # the kernel read clamped ids; the scatter must not leave the table either.  Row 0 is the padding id: its rows of g_hp
+        # are zeros and are skipped
+        g_item = torch.zeros_like(item_weight)
+        ids = history.reshape(-1).clamp(0, item_weight.shape[0] - 1)
+        scatter_add_rows(g_item, ids, g_hp.view(-1, g_hp.shape[2]), padding_idx=0)
+        return g_item, gpos, gW1, gb1, gW2, gb2, None, None
+
+
+def interest_pool(item_weight, pos_weight, history, W1, b1, W2, b2, err_word=None):
+    """interest_pool_fwd under autograd: [B, K, D] whose backward hands back the kernel's gradients of all six parameters (the
+    item table's through scatter_add_rows of g_hp, sorted and deterministic)."""
+    return _InterestPool.apply(item_weight, pos_weight, W1, b1, W2, b2, history, err_word)
+
+
 def sgd_dense(tab, grad, lr, l2=0.0, stamp=None, step_id=0):
     abi.check(abi.lib().wr_sgd_dense(_p(_req(tab, torch.float32, "tab", 2)), tab.shape[0], tab.shape[1],
                                      _p(_req(grad, torch.float32, "grad", 2)), _p(stamp), step_id, lr, l2, _stream()),

@@ -357,9 +357,20 @@ def make_hip_runner(base_runner_cls):
         def _has_query_protocol(model):
             return hasattr(model, "eval_queries") and hasattr(model, "eval_items")
 
+        @staticmethod
+        def _has_interest_protocol(model):
+            """several query vectors per row (``eval_interests`` / ``eval_items``: IF4Rec), scored by their maximum"""
+            return hasattr(model, "eval_interests") and hasattr(model, "eval_items")
+
+        def _refuse_multi_interest(self, model, what):
+            if self._has_interest_protocol(model) and not self._has_query_protocol(model):
+                raise NotImplementedError("%s scores a row by the maximum over several interest vectors (eval_interests): "
+                                          "HipRunner.%s has no top-K over several interests" % (type(model).__name__, what))
+
         def _seq_eval_ok(self, dataset):
-            """--seq_eval_native 1 and a sequential dataset whose model has the query protocol and an embedding size the
-            kernels take; anything else under the flag is logged once and evaluated as without it"""
+            """--seq_eval_native 1 and a sequential dataset whose model has the query protocol (or the interest protocol, with a
+            number of interests wr_rank_eval_multi takes) and an embedding size the kernels take; anything else under the flag
+            is logged once and evaluated as without it"""
             if not self.seq_eval_native:
                 return False
             from . import hip_ops
@@ -367,6 +378,11 @@ def make_hip_runner(base_runner_cls):
             why = None
             if "position" not in dataset.data:
                 why = "the dataset is not sequential"
+            elif self._has_interest_protocol(model) and not self._has_query_protocol(model) and hasattr(model, "history_max"):
+                D, K = model.eval_items().shape[1], int(model.n_interests)
+                if not hip_ops.rank_eval_multi_supports(D, K):
+                    why = ("the multi-interest ranking kernel does not take %d interests of size %d (1, 2 or 4 interests)"
+                           % (K, D))
             elif not self._has_query_protocol(model) or not hasattr(model, "history_max"):
                 why = "%s has no eval_queries() / eval_items()" % type(model).__name__
             elif not hip_ops.rank_eval_supports(model.eval_items().shape[1]):
@@ -396,24 +412,41 @@ def make_hip_runner(base_runner_cls):
                 out[lo:lo + step] = model.eval_queries(hist[lo:lo + step], lens[lo:lo + step])
             return out
 
+        def _interests_of(self, model, hist, lens):
+            """[n, K, D] interest vectors through the model's eval_interests, in chunks of eval_batch_size like _queries_of"""
+            n, step = hist.shape[0], max(int(self.eval_batch_size), 1)
+            out = torch.empty((n, int(model.n_interests), model.eval_items().shape[1]), dtype=torch.float32, device=hist.device)
+            for lo in range(0, n, step):
+                out[lo:lo + step] = model.eval_interests(hist[lo:lo + step], lens[lo:lo + step])
+            return out
+
         def rank_rows(self, dataset):
             """Rank of every row's ground-truth item among all (unmasked) items, int64 [n_eval], for a sequential dataset
             whose model has the query protocol: what BaseRunner.interface + evaluate_method compute for it (BaseRunner.py:
             218-258) without the per-sample collate, the [n_eval, n_items] matrix, the Python masking loop and the argsort.
             Histories by array work, queries in chunks of eval_batch_size, then one wr_rank_eval_rows call in which row e
-            scores with its own query and is masked by the lists of its user."""
+            scores with its own query and is masked by the lists of its user.  A model with the interest protocol
+            (``eval_interests``: IF4Rec) goes through wr_rank_eval_multi: a row's score is the maximum over its interests."""
             from . import hip_ops
             model = dataset.model
             consume_loader_seed()                       # the evaluation DataLoader this replaces would draw its base seed
             model.eval()
-            queries = self._row_queries(dataset)
+            multi = self._has_interest_protocol(model) and not self._has_query_protocol(model)
+            if multi:
+                hist, lens = self._history_columns(dataset, next(model.parameters()).device)
+                queries = self._interests_of(model, hist, lens)
+            else:
+                queries = self._row_queries(dataset)
             dev = queries.device
             ptr, idx = self._clicked_mask(dataset.corpus, bool(model.test_all), model.user_num, dev)
             et = torch.from_numpy(np.ascontiguousarray(dataset.data["item_id"])).to(torch.int64).to(dev)
             mrow = None
             if ptr is not None:
                 mrow = torch.from_numpy(np.ascontiguousarray(dataset.data["user_id"])).to(torch.int64).to(dev)
-            rank, _ = hip_ops.rank_eval_rows(queries, model.eval_items().detach().contiguous(), et, mrow, ptr, idx)
+            if multi:
+                rank, _ = hip_ops.rank_eval_multi(queries, model.eval_items().detach().contiguous(), et, mrow, ptr, idx)
+            else:
+                rank, _ = hip_ops.rank_eval_rows(queries, model.eval_items().detach().contiguous(), et, mrow, ptr, idx)
             return rank.cpu().numpy().astype(np.int64)
 
         def _clicked_mask(self, corpus, test_all, n_user_rows, dev):
@@ -444,6 +477,7 @@ def make_hip_runner(base_runner_cls):
             use ``recommend_rows`` for rows of a dataset and ``recommend_next`` for histories given directly."""
             from . import hip_ops
             if not hasattr(model, "eval_factors"):
+                self._refuse_multi_interest(model, "recommend")
                 if self._has_query_protocol(model):
                     raise NotImplementedError("%s scores with one query per row (eval_queries), not per user: use "
                                               "HipRunner.recommend_rows(dataset, k) or recommend_next(model, corpus, "
@@ -490,6 +524,7 @@ def make_hip_runner(base_runner_cls):
 
         def _check_query_model(self, model, k, what):
             from . import hip_ops
+            self._refuse_multi_interest(model, what)
             if not self._has_query_protocol(model) or not hasattr(model, "history_max"):
                 raise NotImplementedError("%s has no eval_queries() / eval_items(): HipRunner.%s needs a sequential model "
                                           "with the query protocol" % (type(model).__name__, what))
@@ -551,6 +586,7 @@ def make_hip_runner(base_runner_cls):
             model = dataset.model
             users = np.asarray(dataset.data["user_id"], dtype=np.int64)
             exclude = "clicked" if model.test_all else "none"
+            self._refuse_multi_interest(model, "save_rec_results (--save_rec)")
             if "position" in dataset.data and self._has_query_protocol(model):      # one query per row, not per user
                 items, _ = self.recommend_rows(dataset, k, exclude=exclude)
             else:
