@@ -997,6 +997,58 @@ int32_t wr_rank_eval_multi(const float *query_mat, int64_t n_query_rows, const f
                            int32_t KQ, const int64_t *eval_target, int64_t n, const int64_t *mask_row, int64_t n_mask_rows,
                            const int64_t *mask_ptr, const int32_t *mask_idx, int32_t *rank, float *target_score, void *stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * K20  SGL's augmented graph views (src/utils/augmentor.py:33-111, csr2tensor of src/models/general/SGL.py:105-146) built on
+ *      the device from a resident BASE: the directed edge list (rows, cols) int32 [n_edges] of the symmetric adjacency over
+ *      n_nodes nodes, sorted by (row, col) without duplicates; mirror int32 [n_edges], the position of (cols[e], rows[e]);
+ *      bchunk_ptr int64 [n_bchunks + 1], the base rows cut into chunks of at most 64 edges that never cross a row, every row
+ *      owning at least one (an empty one for an empty row), in row order; row_first_chunk int64 [n_nodes + 1], the first
+ *      chunk of each row (entry n_nodes = n_bchunks); dis_tab fp32 [n_dis], (c + 1e-10)^-1/2 for c = 0 .. n_dis - 1, host-built,
+ *      n_dis > the largest base degree.
+ *   selection  perm = the keyed bijection of wr_epoch_shuffle with key (seed, stream id in the epoch slot).
+ *              WR_VIEW_EDGE_DROP: edge e is kept iff perm_{stream_id0}(e) < n_select (n_select edges survive; stream_id1 unused).
+ *              WR_VIEW_NODE_DROP: row node v is dropped iff perm_{stream_id0}(v) < n_select, column node v iff
+ *              perm_{stream_id1}(v) < n_select; an edge is kept iff neither its row node nor its column node is dropped.
+ *   view       forward CSR: the kept edges in base order; transposed CSR: row a lists b iff edge (b, a) is kept, ascending;
+ *              val(a, b) = dis_tab[cnt[a]] * dis_tab[cnt[b]] with cnt = kept edges per ROW of the forward view (one fp32
+ *              multiply: bitwise the host's norm_csr / transpose_csr for the same kept set).
+ *   Three calls per view with two scans by the caller between them; nothing is read back inside any of them:
+ *   - wr_sgl_view_count: the keep flags into the workspace, then cnt_fwd / cnt_bwd int32 [n_bchunks], the kept edges of each
+ *     base chunk in the forward / the transposed view.  The caller scans both into scan_* int64 [n_bchunks + 1] (exclusive,
+ *     entry 0 = 0; the last entry is the view's nnz).
+ *   - wr_sgl_view_rows: row_ptr_fwd / row_ptr_bwd int64 [n_nodes + 1] from the scans.
+ *   - wr_sgl_view_fill: col int32 / val fp32 [nnz] of both directions (NULL allowed where nnz = 0) from the SAME workspace the
+ *     count call filled.  nnz_* are the sizes of the arrays: nothing is stored at or past them.
+ *   - workspace >= wr_sgl_views_workspace_bytes(n_nodes, n_edges), 16-byte aligned.  n_edges, n_nodes in [1, 2^31); a size, a
+ *     kind or an n_select outside its range, a NULL array or a short workspace is refused (WR_E_*) before any launch.
+ *   - err_word (int32 on the device, may be NULL; the caller clears and reads it) receives bits for base arrays that
+ *     contradict the contract (1 node id, 2 chunk table, 4 mirror, 8 degree past dis_tab, 16 scan past nnz); such an element is
+ *     skipped or clamped, never addressed.
+ *   - Deterministic: no float atomics, one writer per output element.  No allocation.
+ *   Chunk tables of the load-balanced product (wr_spmm_csr_chunked*) for a device row_ptr int64 [n_rows + 1]:
+ *   - wr_spmm_chunks_count: per[r] = max(1, ceil(deg_r / max_nnz)) int64 [n_rows]; max_per (int32, zeroed by the caller) receives
+ *     the largest.  The caller scans per into chunk_first int64 [n_rows + 1] (exclusive; the last entry is n_chunks).
+ *   - wr_spmm_chunks_fill: chunk_ptr int64 [n_chunks + 1] (chunk k of row r starts at row_ptr[r] + k max_nnz; the last entry is
+ *     row_ptr[n_rows]) and chunk_row int32 [n_chunks]. */
+#define WR_VIEW_EDGE_DROP 0
+#define WR_VIEW_NODE_DROP 1
+int64_t wr_sgl_views_workspace_bytes(int64_t n_nodes, int64_t n_edges);
+int32_t wr_sgl_view_count(int32_t kind, const int32_t *rows, const int32_t *cols, const int32_t *mirror, int64_t n_edges,
+                          int64_t n_nodes, const int64_t *bchunk_ptr, int64_t n_bchunks, int64_t n_select, uint64_t seed,
+                          uint64_t stream_id0, uint64_t stream_id1, int32_t *cnt_fwd, int32_t *cnt_bwd, int32_t *err_word,
+                          void *workspace, int64_t workspace_bytes, void *stream);
+int32_t wr_sgl_view_rows(const int64_t *row_first_chunk, int64_t n_nodes, int64_t n_bchunks, const int64_t *scan_fwd,
+                         const int64_t *scan_bwd, int64_t *row_ptr_fwd, int64_t *row_ptr_bwd, void *stream);
+int32_t wr_sgl_view_fill(const int32_t *rows, const int32_t *cols, const int32_t *mirror, int64_t n_edges, int64_t n_nodes,
+                         const int64_t *bchunk_ptr, int64_t n_bchunks, const int64_t *scan_fwd, const int64_t *scan_bwd,
+                         const int64_t *row_ptr_fwd, const float *dis_tab, int64_t n_dis, int32_t *col_fwd, float *val_fwd,
+                         int64_t nnz_fwd, int32_t *col_bwd, float *val_bwd, int64_t nnz_bwd, int32_t *err_word,
+                         const void *workspace, int64_t workspace_bytes, void *stream);
+int32_t wr_spmm_chunks_count(const int64_t *row_ptr, int64_t n_rows, int32_t max_nnz, int64_t *per, int32_t *max_per,
+                             void *stream);
+int32_t wr_spmm_chunks_fill(const int64_t *row_ptr, int64_t n_rows, int32_t max_nnz, const int64_t *chunk_first, int64_t n_chunks,
+                            int64_t *chunk_ptr, int32_t *chunk_row, void *stream);
+
 /* LightGCN.predict's per-batch tail in two launches (src/models/general/LightGCN.py:156-175, src/utils/loss.py:37-39,94-98):
  *   loss[0] = mean_b( -log(1e-10 + sigmoid(<Ua[u_b], Ia[p_b]> - <Ua[u_b], Ia[n_b]>)) )
  *             + reg_weight * (||U0[u]||_F + ||I0[p]||_F + ||I0[n]||_F) / B

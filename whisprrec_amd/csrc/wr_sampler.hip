@@ -9,6 +9,7 @@
 // host path in whisprrec_amd/host.py keeps the bit-exact NumPy sampler for small-scale parity; the oracle restates THIS
 // generator in NumPy and tests compare bit for bit.
 #include "wr_common.h"
+#include "wr_shuffle.h"
 
 namespace wr {
 
@@ -106,30 +107,7 @@ __global__ __launch_bounds__(kBlock) void sample_negatives_kernel(const Idx *__r
 // XORed with a splitmix64 hash of the other half, the round number and the (seed, epoch) key; kShuffleRounds rounds) with
 // cycle walking (re-apply until the value is < n; the domain is < 2n, so < 2 evaluations on average).  Rows are
 // independent; the result equals oracle.epoch_permutation bit for bit.  Like the device sampler it is NOT the reference's
-// RNG stream: the bit-exact host path stays available.
-constexpr int kShuffleRounds = 8;
-
-__host__ __device__ __forceinline__ uint64_t shuffle_index(uint64_t i, uint64_t n, unsigned bits, uint64_t key) {
-    const unsigned a = bits >> 1, b = bits - a;              // widths of the high and the low half (b >= a >= 1)
-    const uint64_t mask_a = (uint64_t(1) << a) - 1, mask_b = (uint64_t(1) << b) - 1;
-    uint64_t x = i;
-    do {
-        uint64_t hi = x >> b, lo = x & mask_b;
-#pragma unroll
-        for (int r = 0; r < kShuffleRounds; ++r) {
-            if ((r & 1) == 0) hi ^= mix64(key ^ (lo * 0xD1B54A32D192ED03ull + (uint64_t)r)) & mask_a;
-            else lo ^= mix64(key ^ (hi * 0xD1B54A32D192ED03ull + (uint64_t)r)) & mask_b;
-        }
-        x = (hi << b) | lo;
-    } while (x >= n);
-    return x;
-}
-
-static inline unsigned shuffle_bits(int64_t n) {
-    unsigned bits = 2;
-    while (bits < 62 && (int64_t(1) << bits) < n) ++bits;
-    return bits;
-}
+// RNG stream: the bit-exact host path stays available.  shuffle_index / shuffle_bits / shuffle_key: wr_shuffle.h.
 
 template <typename Idx>
 __global__ __launch_bounds__(kBlock) void epoch_shuffle_kernel(const Idx *__restrict__ c0, const Idx *__restrict__ c1,
@@ -155,7 +133,7 @@ static int32_t epoch_shuffle(const Idx *c0, const Idx *c1, const Idx *c2, int64_
     WR_REQUIRE((c0 == nullptr || c0 != o0) && (c1 == nullptr || c1 != o1) && (c2 == nullptr || c2 != o2), WR_E_NULL,
                "shuffle: in-place permutation is not supported");
     if (n == 0) return WR_OK;
-    const uint64_t key = mix64(mix64(seed ^ (epoch * 0x9E3779B97F4A7C15ull)) ^ 0x5DEECE66Dull);
+    const uint64_t key = shuffle_key(seed, epoch);
     hipLaunchKernelGGL((epoch_shuffle_kernel<Idx>), dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0,
                        reinterpret_cast<hipStream_t>(stream), c0, c1, c2, n, shuffle_bits(n), key, o0, o1, o2, order);
     WR_LAUNCH_CHECK("epoch_shuffle_kernel");
@@ -220,7 +198,7 @@ static int32_t epoch_prepare_range(const Idx *users, const Idx *items, int64_t n
     WR_REQUIRE(first >= 0 && count >= 0 && first + count <= n, WR_E_RANGE, "epoch prepare: rows [%lld,%lld) outside the epoch's %lld",
                (long long)first, (long long)(first + count), (long long)n);
     if (count == 0) return WR_OK;
-    const uint64_t key = mix64(mix64(seed ^ (epoch * 0x9E3779B97F4A7C15ull)) ^ 0x5DEECE66Dull);
+    const uint64_t key = shuffle_key(seed, epoch);
     const dim3 grid((unsigned)((count + kBlock - 1) / kBlock));
     if (packed)
         hipLaunchKernelGGL((epoch_prepare_range_kernel<Idx, ClickedPairs, true>), grid, dim3(kBlock), 0,

@@ -2498,6 +2498,164 @@ def spmm_csr_chunked(chunk_ptr, chunk_row, col, val, X, Y=None, acc=None, partia
     return Y
 
 
+# ----------------------------------------------------------------------------------------------- SGL views on the device
+SGL_VIEW_BASE_CHUNK = 64         # base edges per wave of the view builder (wr_views.hip: one ballot per chunk)
+SGL_VIEW_KINDS = {"ED": 0, "ND": 1}
+
+
+def _chunks_count(row_ptr):
+    """first half of spmm_chunks on the device -> (chunk_first int64 [n_rows + 1], max_per int32 [1]); nothing is read back"""
+    _req(row_ptr, torch.int64, "row_ptr", 1)
+    n_rows = row_ptr.numel() - 1
+    dev = row_ptr.device
+    per = torch.empty(n_rows, dtype=torch.int64, device=dev)
+    max_per = torch.zeros(1, dtype=torch.int32, device=dev)
+    abi.check(abi.lib().wr_spmm_chunks_count(_p(row_ptr), n_rows, SPMM_CHUNK_NNZ, _p(per), _p(max_per), _stream()),
+              "wr_spmm_chunks_count")
+    chunk_first = torch.zeros(n_rows + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(per, 0, out=chunk_first[1:])
+    return chunk_first, max_per
+
+
+def _chunks_fill(row_ptr, chunk_first, n_chunks, max_per):
+    """second half: the tables for the sizes read back -> (chunk_ptr, chunk_row) with ``_wr_levels`` set"""
+    dev = row_ptr.device
+    chunk_ptr = torch.empty(n_chunks + 1, dtype=torch.int64, device=dev)
+    chunk_row = torch.empty(n_chunks, dtype=torch.int32, device=dev)
+    abi.check(abi.lib().wr_spmm_chunks_fill(_p(row_ptr), row_ptr.numel() - 1, SPMM_CHUNK_NNZ, _p(chunk_first), n_chunks,
+                                            _p(chunk_ptr), _p(chunk_row), _stream()), "wr_spmm_chunks_fill")
+    chunk_row._wr_levels = 1 if int(max_per) <= SPMM_ONE_LEVEL_MAX_CHUNKS else 2
+    return chunk_ptr, chunk_row
+
+
+def spmm_chunks_device(row_ptr):
+    """spmm_chunks for a row_ptr that lives on the device (wr_spmm_chunks_count / _fill): the same (chunk_ptr, chunk_row), as
+    device tensors, chunk_row carrying ``_wr_levels``.  One read-back (number of chunks, longest row)."""
+    chunk_first, max_per = _chunks_count(row_ptr)
+    n_chunks, mp = torch.cat([chunk_first[-1:], max_per.to(torch.int64)]).tolist()
+    return _chunks_fill(row_ptr, chunk_first, n_chunks, mp)
+
+
+class SglViewsBase:
+    """The device-resident base of SGL's views (sgl_views_base): uploaded once per model"""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def sgl_views_base(rows, cols, n_nodes, device):
+    """Upload the base of the device view builder: the directed edge list (rows, cols) of the symmetric adjacency over n_nodes
+    nodes, sorted by (row, col) with distinct pairs (sgl.adjacency_edges), its row_ptr, the mirror index (position of
+    (cols[e], rows[e])), the table of (c + 1e-10)^-1/2 for every possible degree — the host expression of sgl.norm_csr, so the
+    device values carry its bits — and the 64-edge chunks of the base rows.  ValueError for a list that is not such a base,
+    WhisprRecHipError for a shape the library refuses."""
+    import numpy as np
+    from .sgl import degree_scale
+    rows, cols = np.asarray(rows, dtype=np.int64), np.asarray(cols, dtype=np.int64)
+    n_nodes, E = int(n_nodes), int(rows.size)
+    if cols.size != E:
+        raise ValueError("rows and cols must have one length")
+    abi.check_size(abi.lib().wr_sgl_views_workspace_bytes(n_nodes, E), "wr_sgl_views_workspace_bytes")
+    if rows.min() < 0 or cols.min() < 0 or rows.max() >= n_nodes or cols.max() >= n_nodes:
+        raise ValueError("node id outside [0, n_nodes)")
+    keys = rows * n_nodes + cols
+    if E > 1 and not np.all(keys[1:] > keys[:-1]):
+        raise ValueError("the base edge list must be sorted by (row, col) and hold every pair once")
+    mkeys = cols * n_nodes + rows
+    mirror = np.minimum(np.searchsorted(keys, mkeys), E - 1)
+    if not np.array_equal(keys[mirror], mkeys):
+        raise ValueError("the base edge list must be symmetric: (c, r) for every (r, c)")
+    cnt = np.bincount(rows, minlength=n_nodes)
+    row_ptr = np.zeros(n_nodes + 1, np.int64)
+    np.cumsum(cnt, out=row_ptr[1:])
+    bchunk_ptr, bchunk_row = spmm_chunks(row_ptr, SGL_VIEW_BASE_CHUNK)
+    per = np.bincount(bchunk_row.numpy(), minlength=n_nodes)
+    row_first_chunk = np.zeros(n_nodes + 1, np.int64)
+    np.cumsum(per, out=row_first_chunk[1:])
+    dis_tab = degree_scale(np.arange(int(cnt.max()) + 1, dtype=np.int64))
+
+    def up(a, dt):
+        return torch.from_numpy(np.ascontiguousarray(a.astype(dt))).to(device)
+
+    return SglViewsBase(n_nodes=n_nodes, n_edges=E, device=torch.device(device), rows=up(rows, np.int32), cols=up(cols, np.int32),
+                        mirror=up(mirror, np.int32), row_ptr=up(row_ptr, np.int64), bchunk_ptr=bchunk_ptr.to(device),
+                        n_bchunks=int(bchunk_row.numel()), row_first_chunk=up(row_first_chunk, np.int64),
+                        dis_tab=up(dis_tab, np.float32))
+
+
+class _SglViewBuild:
+    """One view between its two device phases: count (flags, per-chunk counts, scans, row_ptr, chunk counts) and, once the
+    sizes are on the host, fill.  `meta` holds the six numbers fill needs, on the device."""
+
+    def __init__(self, base, kind, n_select, seed, stream_ids):
+        if kind not in SGL_VIEW_KINDS:
+            raise ValueError("kind must be 'ED' or 'ND' (got %r)" % (kind,))
+        ids = [int(s) for s in stream_ids]
+        if len(ids) != (1 if kind == "ED" else 2):
+            raise ValueError("ED takes one stream id (edges), ND two (row nodes, column nodes)")
+        self.base = b = base
+        dev, L, M = b.device, abi.lib(), (1 << 64) - 1
+        nbytes = abi.check_size(L.wr_sgl_views_workspace_bytes(b.n_nodes, b.n_edges), "wr_sgl_views_workspace_bytes")
+        self.ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        self.err = torch.zeros(1, dtype=torch.int32, device=dev)
+        cnt = torch.empty((2, b.n_bchunks), dtype=torch.int32, device=dev)
+        abi.check(L.wr_sgl_view_count(SGL_VIEW_KINDS[kind], _p(b.rows), _p(b.cols), _p(b.mirror), b.n_edges, b.n_nodes,
+                                      _p(b.bchunk_ptr), b.n_bchunks, int(n_select), int(seed) & M, ids[0] & M, ids[-1] & M,
+                                      _p(cnt[0]), _p(cnt[1]), _p(self.err), _p(self.ws), nbytes, _stream()), "wr_sgl_view_count")
+        self.scan = torch.zeros((2, b.n_bchunks + 1), dtype=torch.int64, device=dev)
+        self.scan[:, 1:].copy_(torch.cumsum(cnt, 1, dtype=torch.int64))
+        self.row_ptr = torch.empty((2, b.n_nodes + 1), dtype=torch.int64, device=dev)
+        abi.check(L.wr_sgl_view_rows(_p(b.row_first_chunk), b.n_nodes, b.n_bchunks, _p(self.scan[0]), _p(self.scan[1]),
+                                     _p(self.row_ptr[0]), _p(self.row_ptr[1]), _stream()), "wr_sgl_view_rows")
+        self.chunks = [_chunks_count(self.row_ptr[d]) for d in (0, 1)]
+        self.meta = torch.cat([self.scan[:, -1], self.chunks[0][0][-1:], self.chunks[1][0][-1:],
+                               self.chunks[0][1].to(torch.int64), self.chunks[1][1].to(torch.int64), self.err.to(torch.int64)])
+
+    META = 7
+
+    def fill(self, meta, chunk_tables=True):
+        """meta: the META numbers of self.meta on the host -> per direction (row_ptr, col, val[, chunk_ptr, chunk_row])"""
+        b, dev = self.base, self.base.device
+        nnz, n_chunks, max_per = meta[0:2], meta[2:4], meta[4:6]
+        if meta[6]:
+            raise abi.WhisprRecHipError("wr_sgl_view_count: the base arrays contradict their contract (err_word %d)" % meta[6])
+        col = [torch.empty(n, dtype=torch.int32, device=dev) for n in nnz]
+        val = [torch.empty(n, dtype=torch.float32, device=dev) for n in nnz]
+        abi.check(abi.lib().wr_sgl_view_fill(_p(b.rows), _p(b.cols), _p(b.mirror), b.n_edges, b.n_nodes, _p(b.bchunk_ptr),
+                                             b.n_bchunks, _p(self.scan[0]), _p(self.scan[1]), _p(self.row_ptr[0]), _p(b.dis_tab),
+                                             b.dis_tab.numel(), _p(col[0]) if nnz[0] else None, _p(val[0]) if nnz[0] else None,
+                                             nnz[0], _p(col[1]) if nnz[1] else None, _p(val[1]) if nnz[1] else None, nnz[1],
+                                             _p(self.err), _p(self.ws), self.ws.numel(), _stream()), "wr_sgl_view_fill")
+        out = []
+        for d in (0, 1):
+            part = (self.row_ptr[d], col[d], val[d])
+            if chunk_tables:
+                part += _chunks_fill(self.row_ptr[d], self.chunks[d][0], n_chunks[d], max_per[d])
+            out.append(part)
+        return out
+
+
+def sgl_views_build(base, kind, specs, seed, chunk_tables=True, err_words=None):
+    """Several views of one base with ONE read-back: specs = [(n_keep_or_n_drop, stream_ids), ...] -> per view
+    [forward, transposed], each (row_ptr, col, val, chunk_ptr, chunk_row) on the device (chunk_row carries ``_wr_levels``)."""
+    builds = [_SglViewBuild(base, kind, n, seed, ids) for n, ids in specs]
+    meta = torch.cat([v.meta for v in builds]).tolist()          # the one device-to-host read: sizes of every array
+    K = _SglViewBuild.META
+    out = [v.fill(meta[i * K:(i + 1) * K], chunk_tables) for i, v in enumerate(builds)]
+    if err_words is not None:        # the fill launches' own bits (8, 16: unreachable for scans of the same flags) for who asks
+        err_words.extend(v.err for v in builds)
+    return out
+
+
+def sgl_view(base, kind, n_keep_or_n_drop, seed, stream_ids):
+    """One view of the device base (wr_sgl_view_*): kind 'ED' keeps the n_keep edges e with perm(e) < n_keep, kind 'ND' drops
+    the n_drop row nodes and the n_drop column nodes with perm(v) < n_drop (stream_ids: one id for ED, (rows, cols) for ND;
+    perm = oracle.epoch_permutation_at(., n, seed, stream id)).  Returns the device triples (row_ptr int64, col int32, val
+    fp32) of the view and of its transpose — bitwise sgl.norm_csr / sgl.transpose_csr of the same kept set."""
+    (fwd, bwd), = sgl_views_build(base, kind, [(n_keep_or_n_drop, stream_ids)], seed, chunk_tables=False)
+    return fwd, bwd
+
+
 class HybridSpmm:
     """Normalised-adjacency product with the dense head of the item popularity on the matrix cores (wr_spmm_mfma.hip) and
     the rest on the chunked CSR kernels.  Built once per graph from the symmetric bipartite CSR of LightGCN

@@ -10,7 +10,10 @@ What changes underneath:
   * the adjacency is an edge list in the row-major order ``scipy``'s ``nonzero()`` gives the reference (:81-103), never a
     DOK/LIL matrix and never dense (the reference multiplies ``to_dense()`` N x N views on CPU, :145-146);
   * the views draw from the SAME ``random.sample`` calls in the same order (augmentor.py:52-53,94), so a given ``random``
-    seed drops the same edges / nodes; the construction around them is vectorised NumPy (no ``sp.diags`` products);
+    seed drops the same edges / nodes; the construction around them is vectorised NumPy (no ``sp.diags`` products).
+    ``--views_native 1`` builds them on the device instead (``hip_ops.sgl_views_build``, wr_views.hip): the same uniform
+    exact-size subsets, drawn by a keyed bijection keyed by ``--random_seed`` and ``view_stream`` — the reference's
+    distribution, NOT its ``random`` stream; bitwise ``norm_csr`` / ``transpose_csr`` / ``spmm_chunks`` of the same kept set;
   * views are NOT symmetric (the reference drops (u,i) and (i,u) independently, and normalises by row sums on both
     sides, SGL.py:117-124) — so each view keeps a CSR of its transpose for the backward propagation;
   * the three propagations (:232-239) and their backward run on the chunked CSR SpMM kernel (``wr_spmm_csr_chunked``), row
@@ -71,6 +74,20 @@ def node_dropout_edges(n_nodes, rows, cols, dropout_rate):
     return rows[m], cols[m]
 
 
+def degree_scale(cnt):
+    """(d + 1e-10)^-1/2 in float32 for integer row sums d (csr2tensor, SGL.py:117-124) — the one expression behind norm_csr's
+    values and behind the degree table of the device view builder (hip_ops.sgl_views_base)"""
+    deg = np.asarray(cnt).astype(np.float32) + np.float32(1e-10)
+    return np.power(deg, np.float32(-0.5)).astype(np.float32)
+
+
+def view_stream(version, view, role):
+    """stream id of one draw of the device view builder (--views_native 1): version = graph_construction() calls so far
+    (>= 1), view 0 / 1 = sub1 / sub2, role 0 = edges (ED) or row nodes (ND), 1 = column nodes (ND).  It takes the epoch's
+    place in the keyed bijection (oracle.epoch_permutation_at(x, n, seed, stream))."""
+    return 4 * int(version) + 2 * int(view) + int(role)
+
+
 def norm_csr(n_nodes, rows, cols):
     """csr2tensor (SGL.py:105-146) on an edge list: value(r,c) = d_r^-1/2 * 1 * d_c^-1/2 with d = ROW sums + 1e-10, all in
     float32 like the reference's float32 matrices.  Returns (row_ptr int64 [N+1], col int32, val float32), columns
@@ -78,8 +95,7 @@ def norm_csr(n_nodes, rows, cols):
     order = np.lexsort((cols, rows))
     rows, cols = rows[order], cols[order]
     cnt = np.bincount(rows, minlength=n_nodes)
-    deg = cnt.astype(np.float32) + np.float32(1e-10)
-    dis = np.power(deg, np.float32(-0.5)).astype(np.float32)
+    dis = degree_scale(cnt)
     val = (dis[rows] * np.float32(1.0)) * dis[cols]
     row_ptr = np.zeros(n_nodes + 1, np.int64)
     np.cumsum(cnt, out=row_ptr[1:])
@@ -103,6 +119,17 @@ class CsrGraph:
         self.fwd = self._upload(row_ptr, col, val, device)
         self.bwd = self.fwd if symmetric else self._upload(*transpose_csr(n_nodes, row_ptr, col, val), device)
         self._partials = None
+
+    @classmethod
+    def from_device_parts(cls, n_nodes, fwd, bwd):
+        """a view whose chunked CSRs already live on the device (hip_ops.sgl_views_build): fwd / bwd = (row_ptr, col, val,
+        chunk_ptr, chunk_row) of A and of A^T, chunk_row carrying ``_wr_levels``"""
+        g = cls.__new__(cls)
+        g.n = n_nodes
+        g.fwd, g.bwd = ((p[3], p[4], p[1], p[2]) for p in (fwd, bwd))
+        g.row_ptr = (fwd[0], bwd[0])
+        g._partials = None
+        return g
 
     @staticmethod
     def _upload(row_ptr, col, val, device):
@@ -167,6 +194,9 @@ def make_sgl(general_model_cls):
             parser.add_argument("--drop_ratio", type=float, default=0.1, help="The dropout ratio.")
             parser.add_argument("--ssl_native", type=int, default=0, choices=[0, 1],
                                 help="1: InfoNCE loss and gradient by the fused HIP kernels (no [B, n] matrix); 0: torch GEMMs + autograd.")
+            parser.add_argument("--views_native", type=int, default=0, choices=[0, 1],
+                                help="1: the epoch's two views are built on the device (keyed bijection, not Python's random "
+                                     "stream); 0: host views from random.sample, the reference's stream.")
             return general_model_cls.parse_model_args(parser)
 
         def __init__(self, args, corpus):
@@ -181,6 +211,10 @@ def make_sgl(general_model_cls):
             self.ssl_weight, self.ssl_tau, self.drop_ratio = args.ssl_weight, args.ssl_tau, args.drop_ratio
             self.ssl_native = bool(int(getattr(args, "ssl_native", 0)))
             self._ssl_native_ok = None   # decided at the first step: the library says which embedding sizes it takes
+            self.views_native = bool(int(getattr(args, "views_native", 0)))
+            self.views_seed = int(getattr(args, "random_seed", 0))
+            self._views_native_ok = None # False once the library has refused this graph (logged once)
+            self._views_base = None      # device base of the view builder, uploaded at the first native construction
             self.user_embedding = nn.Embedding(self.n_users, self.emb_size)
             self.item_embedding = nn.Embedding(self.n_items, self.emb_size)
             # plain attributes like the reference's graphs (absent from state_dict)
@@ -200,10 +234,13 @@ def make_sgl(general_model_cls):
             return getattr(self, "_views_version", 0)
 
         def graph_construction(self):
-            """two views per epoch from Python's ``random`` stream, in the reference's order (SGL.py:67-79)"""
+            """two views per epoch from Python's ``random`` stream, in the reference's order (SGL.py:67-79); with
+            --views_native 1 from the keyed bijection on the device (same distribution, another stream: DESIGN.md)"""
             self._views_version = getattr(self, "_views_version", 0) + 1
             N = self.n_users + self.n_items
             rows, cols = self._edges
+            if self.views_native and self.type in ("ED", "ND") and self._construct_views_native(N, rows, cols):
+                return
             for name in ("sub1", "sub2"):
                 self._graphs_dev.pop(name, None)
                 if self.type == "ND":
@@ -215,6 +252,35 @@ def make_sgl(general_model_cls):
                     continue
                 self._graphs[name] = (norm_csr(N, r, c), False)
 
+        def _construct_views_native(self, N, rows, cols):
+            """--views_native 1: both views, forward and transposed, with their chunk tables straight into _graphs_dev from the
+            device-resident base (hip_ops.sgl_views_build: no per-edge host work, no upload, one read-back of the array
+            sizes).  False (logged once): the library refuses the shape and the host path goes on."""
+            dev = self.user_embedding.weight.device
+            if self._views_native_ok is False or dev.type != "cuda":
+                return False
+            try:
+                if self._views_base is None or self._views_base.device != dev:
+                    self._views_base = hip_ops.sgl_views_base(rows, cols, N, dev)
+            except (ValueError, hip_ops.abi.WhisprRecHipError) as e:
+                logging.warning("--views_native 1: the device view builder does not take this graph (%s); keeping the host views", e)
+                self._views_native_ok = False
+                return False
+            v = self._views_version
+            if self.type == "ED":
+                n_sel = int(rows.size * (1 - self.drop_ratio))
+                specs = [(n_sel, (view_stream(v, k, 0),)) for k in (0, 1)]
+            else:
+                n_sel = int(N * self.drop_ratio)
+                specs = [(n_sel, (view_stream(v, k, 0), view_stream(v, k, 1))) for k in (0, 1)]
+            for name, (fwd, bwd) in zip(("sub1", "sub2"), hip_ops.sgl_views_build(self._views_base, self.type, specs,
+                                                                                self.views_seed)):
+                g = CsrGraph.from_device_parts(N, fwd, bwd)
+                g.device = dev
+                self._graphs_dev[name] = g
+                self._graphs[name] = "device"            # built: _graph() finds it in _graphs_dev
+            return True
+
         def _graph(self, name):
             dev = self.user_embedding.weight.device
             g = self._graphs_dev.get(name)
@@ -224,6 +290,11 @@ def make_sgl(general_model_cls):
                     raise AttributeError("graph_construction() has not been called (SGL.Dataset.actions_before_epoch)")
                 if spec is None:
                     g = _IdentityView()
+                elif spec == "device":       # native views of another device: the same version gives the same views again
+                    if not self._construct_views_native(self.n_users + self.n_items, *self._edges):
+                        raise RuntimeError("the device-built views live on %s; call graph_construction() after moving the model"
+                                           % (g.device,))
+                    return self._graphs_dev[name]
                 else:
                     (rp, col, val), sym = spec
                     g = CsrGraph(self.n_users + self.n_items, rp, col, val, dev, symmetric=sym)
