@@ -24,8 +24,19 @@ Measured floors (fp32 C oracle against float64 at probe_lr(B); ids, seeds and ta
     40K x 50K, 64, 2,048, 3, rows with 150 / 200 occurrences  6.5e-2        1.3e-6      1.4e-5
     120K x 150K, 64, 8,192, 9, a row with 600 occurrences     3.2e-1        4.2e-6      1.7e-5
     120K x 150K, 64, 8,192, 9, a row with 100 occurrences     1.1e-1        4.7e-6      1.5e-5
+  the stratified (rotating item blocks) schedule on its GLOBAL batches, B = the ranks' batches together, at probe_lr(B)
+  (tests/test_rotating_power.py):
+    6K x 4,002, 64, 2 x 2,048, 24 (2 ranks, 2 parts, 2 epochs)   6.0e-2        4.0e-6      8.3e-6
+    6K x 4,003, 64, 3 x 2,048, 36 (3 ranks, 2 parts, 2 epochs)   9.7e-2        5.2e-6      8.9e-6
+    6K x 4,004, 64, 4 x 2,048, 72 (4 ranks, 3 parts, 2 epochs)   1.9e-1        2.9e-6      6.1e-6
+    6K x 4,002, 64, 2 x 2,048, 12 (2 real ranks, 1 epoch)        4.6e-2        4.4e-6      9.3e-6
+    6K x 4,003, 64, 3 x 2,048, 18 (3 real ranks, 1 epoch)        6.5e-2        4.1e-6      9.2e-6
+    3K x 2,001, 64, 4,096, 15 (1 rank, 3 sub-epochs)             7.6e-2        3.6e-6      7.4e-6
+    40K x 196,610, 64, 2 x 8,192, 8 (2 ranks, chained launch)    3.9e-2        4.8e-6      1.9e-5
 
     TOL_UPDATE = 8 x 6.8e-6 = 5.4e-5 -> 6e-5          TOL_ROW = 8 x 1.74e-5 = 1.4e-4 -> 2e-4
+    (from the first three rows, as test_parity_power asserts; the largest row floor of the whole table, 1.88e-5 on the chained
+    launch's shape, gives 8 x 1.88e-5 = 1.5e-4 -> 2e-4 as well, and every row leaves the factor 4)
 
 Hot rows run at the same probe_lr(B).  A row with c occurrences does not move c times as far as a row with one: its
 gradient is a sum of c nearly independent rows (~sqrt(c)), and the row with 600 occurrences per batch moves by 0.3 of the

@@ -13,6 +13,8 @@ import torch.multiprocessing as mp
 
 import oracle
 from conftest import rel_err
+from oracle import parity
+from rotating_ref import make_schedule
 from test_sharded_gloo import _free_port
 
 pytestmark = pytest.mark.gpu
@@ -71,59 +73,40 @@ def _worker(rank, world, port, payload, out_dir):
         local = hip_ops.PipelinedSgd(chunk)
         local.PLAN_TRIPLETS = 1                       # plans of exactly `chunk` batches: chunk ends inside and across the strata
         m = RotatingBprmf(nU, nI, D, dev, parts=parts, local=local, transport=StagedGlooTransport())
-        m.load_full(torch.from_numpy(payload["U"]), torch.from_numpy(payload["I"]))
         t = lambda a: torch.from_numpy(a.astype(np.int32)).to(dev)
         sched = [(t(u), t(p), t(n), pp) for (u, p, n, pp) in payload["strata"][rank]]
-        losses = m.run_strata(sched, B, lr)
-        assert m.held == rank                         # a full epoch brings every block home
-        gl = m.global_losses(losses)
-        Uf, If = m.gather_full()
-        torch.cuda.synchronize()
-        if rank == 0:
-            np.savez(os.path.join(out_dir, "out.npz"), U=Uf.cpu().numpy(), I=If.cpu().numpy(), loss=gl.cpu().numpy())
+        for tag, run_lr in (("", lr), ("_probe", payload["probe_lr"])):   # the test's run, then the probe run from the same tables
+            m.load_full(torch.from_numpy(payload["U"]), torch.from_numpy(payload["I"]))
+            losses = m.run_strata(sched, B, run_lr)
+            assert m.held == rank                     # a full epoch brings every block home
+            gl = m.global_losses(losses)
+            Uf, If = m.gather_full()
+            torch.cuda.synchronize()
+            if rank == 0:
+                np.savez(os.path.join(out_dir, "out%s.npz" % tag), U=Uf.cpu().numpy(), I=If.cpu().numpy(), loss=gl.cpu().numpy())
     finally:
         dist.destroy_process_group()
 
 
 @pytest.mark.parametrize("world,parts,chunk", [(2, 2, 2), (3, 2, 64)])
 def test_rotating_epoch_real_ranks_one_gpu_equals_single_process(tmp_path, world, parts, chunk):
-    from whisprrec_amd.sharded import n_local_rows
-    rng = np.random.RandomState(world * 10 + parts)
     nU, nI, D, B, lr = 6000, 4000 + world, 64, 2048, 0.3
     steps_per_part = [3] * parts
-    U = (rng.standard_normal((nU, D)) * 0.3).astype(np.float32)
-    I = (rng.standard_normal((nI, D)) * 0.3).astype(np.float32)
-
-    def part_range(block, k):
-        n = n_local_rows(nI, block, world); per = (n + parts - 1) // parts
-        return min(n, k * per), min(n, (k + 1) * per)
-
-    strata = [[None] * world for _ in range(world)]
-    glob = [[] for _ in range(world)]
-    for rank in range(world):
-        n_loc_u = n_local_rows(nU, rank, world)
-        for r in range(world):
-            held = (rank + r) % world
-            us, ps, ns = [], [], []
-            for k in range(parts):
-                lo, hi = part_range(held, k)
-                cnt = steps_per_part[k] * B
-                us.append(rng.randint(0, n_loc_u, cnt)); ps.append(rng.randint(lo, hi, cnt)); ns.append(rng.randint(lo, hi, cnt))
-            u, p, n = np.concatenate(us), np.concatenate(ps), np.concatenate(ns)
-            strata[rank][r] = (u, p, n, steps_per_part)
-            glob[r].append((u * world + rank, p * world + held, n * world + held))      # back to global ids
-    payload = dict(shape=(nU, nI, D, B, lr, parts, chunk), U=U, I=I, strata=strata)
+    sch = make_schedule(world, parts, 1, nU, nI, D, B, steps_per_part, seed=world * 10 + parts, scale=0.3)
+    U, I, strata = sch.U, sch.I, sch.strata
+    payload = dict(shape=(nU, nI, D, B, lr, parts, chunk), U=U, I=I, strata=strata, probe_lr=parity.probe_lr(B * world))
     mp.spawn(_worker, args=(world, _free_port(), payload, str(tmp_path)), nprocs=world, join=True)
     got = np.load(tmp_path / "out.npz")
     Uo, Io = U.copy(), I.copy()
     ref = []
-    for r in range(world):
-        for k in range(sum(steps_per_part)):
-            sl = slice(k * B, (k + 1) * B)
-            gu = np.concatenate([glob[r][rank][0][sl] for rank in range(world)])
-            gp = np.concatenate([glob[r][rank][1][sl] for rank in range(world)])
-            gn = np.concatenate([glob[r][rank][2][sl] for rank in range(world)])
-            ref.append(oracle.bprmf_step_sgd(Uo, Io, gu, gp, gn, lr, 0.0))              # ONE step over the global batch
+    GB = B * world
+    for k in range(world * sum(steps_per_part)):
+        sl = slice(k * GB, (k + 1) * GB)                                                 # the ranks' k-th batches side by side
+        ref.append(oracle.bprmf_step_sgd(Uo, Io, sch.gu[sl], sch.gp[sl], sch.gn[sl], lr, 0.0))   # ONE step over the global batch
     assert rel_err(got["loss"], np.asarray(ref)) < 1e-5
     assert rel_err(got["U"], Uo) < 1e-5
     assert rel_err(got["I"], Io) < 1e-5
+    # probe run (oracle/parity.py): the global batch is B * world, so lr = probe_lr(B * world)
+    got = np.load(tmp_path / "out_probe.npz")
+    parity.check_sgd_run("rotating %d real ranks, %d parts, plans of %d" % (world, parts, chunk), U, I, sch.gu, sch.gp, sch.gn, GB,
+                         parity.probe_lr(GB), got["U"], got["I"], got["loss"])

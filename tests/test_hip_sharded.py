@@ -12,6 +12,7 @@ import torch.distributed as dist
 import oracle
 from conftest import rel_err
 from oracle import parity
+from rotating_ref import make_schedule
 
 pytestmark = pytest.mark.gpu
 
@@ -124,7 +125,7 @@ def test_rotating_world1_matches_oracle(pg):
     m = RotatingBprmf(nU, nI, D, dev, parts=parts)
     m.load_full(torch.from_numpy(U), torch.from_numpy(I))
     Uo, Io = U.copy(), I.copy()
-    ref, got = [], []
+    ref, got, subs = [], [], []
     for sub in range(3):
         per_part = [2, 3]
         us, ps, ns = [], [], []
@@ -134,6 +135,7 @@ def test_rotating_world1_matches_oracle(pg):
             us.append(rng.randint(0, nU, cnt)); ps.append(rng.randint(lo, hi, cnt)); ns.append(rng.randint(max(lo, 1), hi, cnt))
         u, p, n = np.concatenate(us), np.concatenate(ps), np.concatenate(ns)
         t = lambda a: torch.from_numpy(a).to(dev)
+        subs.append((u, p, n, per_part))
         got.append(m.global_losses(m.run_subepoch(t(u), t(p), t(n), per_part, B, lr)).cpu().numpy())
         for k in range(sum(per_part)):
             sl = slice(k * B, (k + 1) * B)
@@ -142,3 +144,23 @@ def test_rotating_world1_matches_oracle(pg):
     assert rel_err(np.concatenate(got), np.asarray(ref)) < 1e-5
     assert rel_err(Uf.cpu().numpy(), Uo) < 1e-5
     assert rel_err(If.cpu().numpy(), Io) < 1e-5
+    # probe run (oracle/parity.py) from the same tables: the same three sub-epochs at probe_lr(B), measured on the update.
+    # tests/test_rotating_power.py measures this case's fp32 floor from make_schedule: it must draw these very ids
+    sch = make_schedule(1, parts, 3, nU, nI, D, B, [2, 3], seed=21, scale=0.3, neg_from_one=True)
+    u, p, n = (np.concatenate([s[j] for s in subs]) for j in range(3))
+    assert np.array_equal(sch.gu, u) and np.array_equal(sch.gp, p) and np.array_equal(sch.gn, n)
+    probe = parity.probe_lr(B)
+    m.load_full(torch.from_numpy(U), torch.from_numpy(I))
+    losses = [m.global_losses(m.run_subepoch(t(su), t(sp), t(sn), per_part, B, probe)).cpu().numpy() for su, sp, sn, per_part in subs]
+    Uf, If = m.gather_full()
+
+    def one_step_calls(k_steps):
+        """the tables after the first k_steps steps, every step a call of its own on its part"""
+        m.load_full(torch.from_numpy(U), torch.from_numpy(I))
+        for k in range(k_steps):
+            su, sp, sn, per_part = subs[k // 5]
+            sl = slice(k % 5 * B, (k % 5 + 1) * B)
+            m.run_subepoch(t(su[sl]), t(sp[sl]), t(sn[sl]), [1, 0] if k % 5 < per_part[0] else [0, 1], B, probe)
+        return m.gather_full()
+
+    parity.check_sgd_run("rotating, one rank", U, I, u, p, n, B, probe, Uf, If, np.concatenate(losses), per_step=one_step_calls)

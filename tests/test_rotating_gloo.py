@@ -12,6 +12,7 @@ import torch.multiprocessing as mp
 
 import oracle
 from conftest import rel_err
+from rotating_ref import make_schedule
 
 
 class OracleLocal:
@@ -90,31 +91,10 @@ def _free_port():
                                                   (2, 61, 2, "deferred"), (3, 50, 1, "deferred"), (2, 61, 2, "pieces"),
                                                   (3, 70, 2, "pieces")])
 def test_rotating_epoch_equals_single_process(tmp_path, world, nI, parts, whole):
-    from whisprrec_amd.sharded import n_local_rows
-    rng = np.random.RandomState(world * 10 + parts)
     nU, D, B, lr = 53, 16, 32, 0.3
     steps_per_part = [2] * parts
-    U = (rng.standard_normal((nU, D)) * 0.5).astype(np.float32)
-    I = (rng.standard_normal((nI, D)) * 0.5).astype(np.float32)
-
-    def part_range(block, k):
-        n = n_local_rows(nI, block, world); per = (n + parts - 1) // parts
-        return min(n, k * per), min(n, (k + 1) * per)
-
-    strata = [[None] * world for _ in range(world)]
-    glob = [[] for _ in range(world)]                               # per sub-epoch: list over local steps of per-rank batches
-    for rank in range(world):
-        n_loc_u = n_local_rows(nU, rank, world)
-        for r in range(world):
-            held = (rank + r) % world
-            us, ps, ns = [], [], []
-            for k in range(parts):
-                lo, hi = part_range(held, k)
-                cnt = steps_per_part[k] * B
-                us.append(rng.randint(0, n_loc_u, cnt)); ps.append(rng.randint(lo, max(hi, lo + 1), cnt)); ns.append(rng.randint(lo, max(hi, lo + 1), cnt))
-            u, p, n = np.concatenate(us), np.concatenate(ps), np.concatenate(ns)
-            strata[rank][r] = (u.astype(np.int64), p.astype(np.int64), n.astype(np.int64), steps_per_part)
-            glob[r].append((u * world + rank, p * world + held, n * world + held))   # back to global ids
+    sched = make_schedule(world, parts, 1, nU, nI, D, B, steps_per_part, seed=world * 10 + parts, scale=0.5)
+    U, I, strata = sched.U, sched.I, sched.strata
     total = world * sum(steps_per_part)
     cuts = [3, 1, 2] + [total - 6] if total > 6 else [total]       # pieces that end inside parts, on part ends, on stratum ends
     payload = dict(shape=(nU, nI, D, B, lr, parts), U=U, I=I, strata=strata, whole_epoch=whole, cuts=cuts)
@@ -123,13 +103,9 @@ def test_rotating_epoch_equals_single_process(tmp_path, world, nI, parts, whole)
     Uo, Io = U.copy(), I.copy()
     ref = []
     nsteps = sum(steps_per_part)
-    for r in range(world):
-        for k in range(nsteps):
-            sl = slice(k * B, (k + 1) * B)
-            gu = np.concatenate([glob[r][rank][0][sl] for rank in range(world)])
-            gp = np.concatenate([glob[r][rank][1][sl] for rank in range(world)])
-            gn = np.concatenate([glob[r][rank][2][sl] for rank in range(world)])
-            ref.append(oracle.bprmf_step_sgd(Uo, Io, gu, gp, gn, lr, 0.0))           # ONE step over the global batch
+    for k in range(world * nsteps):
+        sl = slice(k * B * world, (k + 1) * B * world)                               # the ranks' k-th batches side by side
+        ref.append(oracle.bprmf_step_sgd(Uo, Io, sched.gu[sl], sched.gp[sl], sched.gn[sl], lr, 0.0))   # ONE step over the global batch
     assert rel_err(got["loss"], np.asarray(ref)) < 1e-5
     assert rel_err(got["U"], Uo) < 1e-5
     assert rel_err(got["I"], Io) < 1e-5
