@@ -1049,6 +1049,29 @@ int32_t wr_spmm_chunks_count(const int64_t *row_ptr, int64_t n_rows, int32_t max
 int32_t wr_spmm_chunks_fill(const int64_t *row_ptr, int64_t n_rows, int32_t max_nnz, const int64_t *chunk_first, int64_t n_chunks,
                             int64_t *chunk_ptr, int32_t *chunk_row, void *stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * K21  ContraRec's two augmented views of a batch of histories (ContraRec.Dataset.augment / mask_op / reorder_op, reference
+ *      src/models/sequential/ContraRec.py:107-129) drawn on the device: the reference's distribution, not NumPy's stream.
+ *   hist int64 [n_rows, T] left-aligned, zero-padded histories; lengths int64 [n_rows]; rows int64 [B], the dataset row ids of
+ *   the batch (any order, repeats allowed); out_a / out_b int64 [B, T], the two views, 0 at every position t >= L.
+ *   Per (row, view): with probability 1/2 mask, otherwise reorder; ratio ~ Beta(beta_a, beta_b), sel = int(L * ratio) in
+ *   float64, truncated (sel <= L - 1).  mask: a uniform subset of sel of the L positions becomes mask_token.  reorder: start
+ *   uniform on [0, L - sel], the window [start, start + sel) permuted uniformly (sel of 0 or 1 leaves the row unchanged).
+ *   - Generator: counter-based on the splitmix64 finaliser, keyed by (seed, epoch, dataset row id, view) and a domain constant
+ *     of its own; no state.  A row's views depend on neither the batch it arrives in nor its position there.
+ *   - Beta(a, b) for integer a, b is the a-th smallest of a + b - 1 uniforms (exact); subset and permutation come from ranking
+ *     64-bit position keys by (key, index) (exact up to key ties, 2^-64 per pair, broken by index); start is the high half of
+ *     draw * (L - sel + 1), within 2^-58 (total variation) of uniform.
+ *   - 1 <= T <= 64, beta_a, beta_b >= 1, beta_a + beta_b - 1 <= 15 (wr_seq_augment_supported); n_rows >= 1, 0 <= B < 2^31.  A
+ *     NULL array, an unsupported shape or a size out of range is refused (WR_E_*) before any launch.
+ *   - err_word (int32 on the device, may be NULL; the caller clears and reads it): bit 1 a length outside [1, T] (clamped before
+ *     it bounds anything), bit 2 a row id outside [0, n_rows) (its two output rows are zeros).  Nothing is read out of bounds.
+ *   - Deterministic: one writer per output element.  One launch, no workspace, no allocation, no host round trip. */
+int32_t wr_seq_augment_supported(int32_t T, int32_t beta_a, int32_t beta_b);
+int32_t wr_seq_augment(const int64_t *hist, const int64_t *lengths, int64_t n_rows, int32_t T, const int64_t *rows, int64_t B,
+                       int64_t mask_token, int32_t beta_a, int32_t beta_b, uint64_t seed, uint64_t epoch, int64_t *out_a,
+                       int64_t *out_b, int32_t *err_word, void *stream);
+
 /* LightGCN.predict's per-batch tail in two launches (src/models/general/LightGCN.py:156-175, src/utils/loss.py:37-39,94-98):
  *   loss[0] = mean_b( -log(1e-10 + sigmoid(<Ua[u_b], Ia[p_b]> - <Ua[u_b], Ia[n_b]>)) )
  *             + reg_weight * (||U0[u]||_F + ||I0[p]||_F + ||I0[n]||_F) / B

@@ -215,6 +215,9 @@ SIGNATURES = {
                                  c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp]),
     "wr_spmm_chunks_count": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp, c_vp]),
     "wr_spmm_chunks_fill": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp]),
+    "wr_seq_augment_supported": (c_i32, [c_i32, c_i32, c_i32]),
+    "wr_seq_augment": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_vp, c_i64, c_i64, c_i32, c_i32, ctypes.c_uint64, ctypes.c_uint64, c_vp,
+                               c_vp, c_vp, c_vp]),
     "wr_lightgcn_loss_workspace_bytes": (c_i64, [c_i64]),
     "wr_lightgcn_loss": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_vp, c_vp, c_vp, c_i64, c_f32, c_vp, c_vp, c_vp,
                                  c_i64, c_vp]),

@@ -14,6 +14,13 @@ to the keys j < length.  Two native paths, both off by default:
                      call, so each keeps the reference's per-call score maximum.
   --ccc_native 1     the contrastive term goes through ``hip_ops.supcon_loss`` (wr_supcon_loss_grad, K15): no [2B, 2B] array.
 A shape the kernels do not take is logged once and keeps the torch path.
+
+The two augmented views of a training row come from ``Dataset._get_feed_dict``, sample by sample from NumPy's global stream, so
+``HipRunner.fit`` leaves this model to the reference's DataLoader loop (``per_sample_feed``).  Off by default:
+  --aug_native 1     the views of a batch are drawn on the device (``hip_ops.seq_augment``, wr_seq_augment, K21) from the runner's
+                     history table, keyed by (--random_seed, epoch, dataset row, view): the reference's distribution, not NumPy's
+                     stream.  The model then trains through ``HipRunner.fit``'s batch loop like SASRec (``train_batch_extras``).
+                     A (history_max, beta_a, beta_b) the kernel does not take is logged once and keeps the host path.
 """
 import logging
 
@@ -82,6 +89,7 @@ def make_contrarec(sequential_model_cls):
         extra_log_args = ["gamma", "num_neg", "batch_size", "ccc_temp"]
         NUM_LAYERS, NUM_HEADS = 2, 2
         per_sample_feed = True       # HipRunner.fit: the augmented views come from Dataset._get_feed_dict, row by row
+                                     # (an instance under --aug_native 1 with a supported shape sets it to False)
 
         @staticmethod
         def parse_model_args(parser):
@@ -94,6 +102,10 @@ def make_contrarec(sequential_model_cls):
                                 help="1: each encoder block by the fused HIP kernels with a key-length mask; 0: torch ops + autograd.")
             parser.add_argument("--ccc_native", type=int, default=0, choices=[0, 1],
                                 help="1: the contrastive loss and its gradient by the fused HIP kernel; 0: torch ops + autograd.")
+            parser.add_argument("--aug_native", type=int, default=0, choices=[0, 1],
+                                help="1: the two augmented views of every batch are drawn on the device and the model trains "
+                                     "through HipRunner's batch loop; the views follow the reference's distribution and are keyed "
+                                     "by --random_seed, but are not NumPy's stream.  0: the reference's per-sample DataLoader loop.")
             return sequential_model_cls.parse_model_args(parser)
 
         def __init__(self, args, corpus):
@@ -109,6 +121,16 @@ def make_contrarec(sequential_model_cls):
             self._block_native_ok = {}   # per history length, decided at its first batch: the library says what it takes
             self._ccc_native_ok = {}     # per batch size
             self._block_err = None       # device error word of the key lengths, read by check_key_lengths()
+            self.aug_native = bool(int(getattr(args, "aug_native", 0)))
+            self.aug_seed = int(getattr(args, "random_seed", 3407))
+            self._aug_table = None       # (histories [n, T], lengths [n]) of the training rows, unshuffled: set_history_table()
+            self._aug_err = None         # device error word of the view builder, read by check_train_extras()
+            if self.aug_native:
+                if hip_ops.seq_augment_supports(self.max_his, self.beta_a, self.beta_b):
+                    self.per_sample_feed = False     # HipRunner.fit: slices of the epoch's device columns + train_batch_extras
+                else:
+                    logging.warning("--aug_native 1: the view builder does not take history_max=%s beta_a=%s beta_b=%s; keeping "
+                                    "the host path", self.max_his, self.beta_a, self.beta_b)
 
         # ------------------------------------------------------------------------------------ native paths
         def _use_block_native(self, T):
@@ -143,6 +165,31 @@ def make_contrarec(sequential_model_cls):
             if self._block_err is not None and int(self._block_err.item()) != 0:
                 self._block_err.zero_()
                 raise IndexError("ContraRec: a history length outside [1, history_max] reached the block kernels")
+
+        # ------------------------------------------------------------------------------------ the views on the device
+        def set_history_table(self, hist, lengths):
+            """HipRunner.fit, once per epoch: the histories [n, T] and lengths [n] of the training rows in dataset order"""
+            self._aug_table = (hist, lengths)
+
+        def train_batch_extras(self, batch, rows, epoch):
+            """HipRunner.fit, per batch: adds the two views of the dataset rows `rows` (device int64 [B]) in epoch `epoch`"""
+            hist, lengths = self._aug_table
+            if self._aug_err is None:
+                self._aug_err = torch.zeros(1, dtype=torch.int32, device=hist.device)
+            batch["history_items_a"], batch["history_items_b"] = hip_ops.seq_augment(
+                hist, lengths, rows, self.mask_token, self.beta_a, self.beta_b, self.aug_seed, epoch, err_word=self._aug_err)
+            return batch
+
+        def check_train_extras(self):
+            """raise if a view builder call since the last check met a length outside [1, T] or a row id outside the table (one
+            read of the device word; HipRunner.fit asks once per epoch)"""
+            if self._aug_err is not None:
+                word = int(self._aug_err.item())
+                if word != 0:
+                    self._aug_err.zero_()
+                    raise IndexError("ContraRec: the view builder met %s" % " and ".join(
+                        t for bit, t in ((1, "a history length outside [1, history_max]"), (2, "a row id outside the history table"))
+                        if word & bit))
 
         # ------------------------------------------------------------------------------------ the reference's methods
         def _encode(self, history, lengths):

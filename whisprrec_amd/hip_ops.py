@@ -1540,6 +1540,48 @@ def supcon_loss(F, labels, tau):
     return _SupCon.apply(F, labels, float(tau))
 
 
+# ----------------------------------------------------------------------------------------------- ContraRec's augmented views (K21)
+def seq_augment_supports(T, beta_a, beta_b):
+    """shapes wr_seq_augment takes (wr_seq_augment_supported): 1 <= T <= 64, integer beta_a, beta_b >= 1, beta_a + beta_b - 1 <= 15"""
+    if int(beta_a) != beta_a or int(beta_b) != beta_b:
+        return False
+    return bool(abi.lib().wr_seq_augment_supported(int(T), int(beta_a), int(beta_b)))
+
+
+def seq_augment(hist, lengths, rows, mask_token, beta_a, beta_b, seed, epoch, err_word=None, out=None):
+    """ContraRec's two augmented views (ContraRec.py:107-129) of the histories of the dataset rows `rows` [B] (any order, repeats
+    allowed) in one launch of wr_seq_augment: hist [n_rows, T] left-aligned and zero-padded, lengths [n_rows] -> (a, b), int64
+    [B, T].  The reference's distribution from a counter-based generator keyed by (seed, epoch, row id, view), not NumPy's stream:
+    a row's views do not depend on the batch.  A length outside [1, T] is clamped and ORs 1, a row id outside the table gives a
+    zero row and ORs 2 into `err_word` (an int32 (1,) device tensor the caller clears and reads, or None).  `out`: a pair of
+    [B, T] int64 tensors to write into."""
+    _req(hist, torch.int64, "hist", 2)
+    _req(lengths, torch.int64, "lengths", 1)
+    if not isinstance(rows, torch.Tensor) or rows.dim() != 1:
+        raise ValueError("rows must be a [B] tensor")
+    rows = _idx64(rows, "rows")
+    n_rows, T = (int(v) for v in hist.shape)
+    B = rows.numel()
+    if lengths.numel() != n_rows:
+        raise ValueError("lengths must hold one entry per row of hist (got %d for %d rows)" % (lengths.numel(), n_rows))
+    if n_rows < 1 or not seq_augment_supports(T, beta_a, beta_b):
+        raise abi.WhisprRecHipError("seq_augment does not support T=%d beta=(%r, %r) n_rows=%d (1 <= T <= 64, integer a, b >= 1, "
+                                    "a + b - 1 <= 15, n_rows >= 1)" % (T, beta_a, beta_b, n_rows))
+    if err_word is not None:
+        _req(err_word, torch.int32, "err_word")
+    if out is None:
+        out = (torch.empty((B, T), dtype=torch.int64, device=hist.device), torch.empty((B, T), dtype=torch.int64, device=hist.device))
+    for t, name in zip(out, ("out[0]", "out[1]")):
+        _req(t, torch.int64, name, 2)
+        if tuple(t.shape) != (B, T):
+            raise ValueError("%s must be [B, T] = %s (got %s)" % (name, (B, T), tuple(t.shape)))
+    mask64 = (1 << 64) - 1
+    abi.check(abi.lib().wr_seq_augment(_p(hist), _p(lengths), n_rows, T, _p(rows), B, int(mask_token), int(beta_a), int(beta_b),
+                                       int(seed) & mask64, int(epoch) & mask64, _p(out[0]), _p(out[1]), _p(err_word), _stream()),
+              "wr_seq_augment")
+    return out[0], out[1]
+
+
 # ----------------------------------------------------------------------------------------------- BUIR (K16, K17)
 def buir_supports(D):
     """embedding sizes wr_buir_loss_grad takes (wr_buir_supported)"""

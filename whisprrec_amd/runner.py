@@ -700,7 +700,8 @@ def make_hip_runner(base_runner_cls):
             model = dataset.model
             sequential = "position" in dataset.data
             # a model whose training rows carry more than (user, positive, negative, history) — ContraRec's two augmented views,
-            # drawn sample by sample from NumPy's global stream — keeps the reference's DataLoader loop
+            # drawn sample by sample from NumPy's global stream — keeps the reference's DataLoader loop, unless it builds them
+            # per batch itself (train_batch_extras: ContraRec under --aug_native 1 clears per_sample_feed)
             if not hasattr(model, "user_num") or (sequential and not hasattr(model, "history_max")) or \
                     getattr(model, "per_sample_feed", False):
                 return base_runner_cls.fit(self, dataset, epoch)
@@ -736,16 +737,22 @@ def make_hip_runner(base_runner_cls):
             model._trusted_indices = True
             losses = []
             hist = None
+            extras = None    # a model's per-batch additions from the dataset rows of the batch (ContraRec's views, --aug_native 1)
             if sequential:   # the per-row histories travel with the shuffle: same batches as the per-sample collate builds
                 hist_all, len_all = self._history_columns(dataset, dev)
                 order = self._last_order.to(dev)
                 hist, hlen = hist_all[order], len_all[order]
+                extras = getattr(model, "train_batch_extras", None)
+                if extras is not None:
+                    model.set_history_table(hist_all, len_all)
 
             def eager_step(lo):
                 batch = {"user_id": cols[0][lo:lo + B], "pos_item": cols[1][lo:lo + B], "neg_items": cols[2][lo:lo + B].unsqueeze(1),
                          "batch_size": min(B, n - lo), "phase": "train"}
                 if hist is not None:
                     batch["history_items"], batch["lengths"] = hist[lo:lo + B], hlen[lo:lo + B]
+                if extras is not None:
+                    extras(batch, order[lo:lo + B], max(epoch, 0))
                 model.optimizer.zero_grad()
                 loss = model.predict(batch)
                 self._loss_shape = tuple(loss.shape)
@@ -773,7 +780,10 @@ def make_hip_runner(base_runner_cls):
                     lo += B
             finally:
                 model._trusted_indices = False
-            return float(torch.stack(losses).mean().cpu())
+            out = float(torch.stack(losses).mean().cpu())
+            if extras is not None:
+                model.check_train_extras()      # one read of the hook's device error word per epoch
+            return out
 
     HipRunner.__qualname__ = "HipRunner"
     return HipRunner
