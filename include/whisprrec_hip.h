@@ -1072,6 +1072,42 @@ int32_t wr_seq_augment(const int64_t *hist, const int64_t *lengths, int64_t n_ro
                        int64_t mask_token, int32_t beta_a, int32_t beta_b, uint64_t seed, uint64_t epoch, int64_t *out_a,
                        int64_t *out_b, int32_t *err_word, void *stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * K22  Row-lazy dense optimizers for a table whose gradient rows come from autograd — the item table of the sequential models
+ *      (nn.Embedding lookups of src/models/sequential/SASRec.py:60,84,105-106 under torch.optim.Adam / SGD(weight_decay),
+ *      src/helpers/BaseRunner.py:120-124,199).  K5 (lazy, exact) without the BPR step kernels: tab / exp_avg / exp_avg_sq /
+ *      last_step / consts as there (last_step[r] = number of the last optimizer step applied to row r).
+ *   - Gather: out[k,:] = row idx[k] as the dense optimizer holds it after step `upto` — the zero-gradient steps last_step[r]+1 ..
+ *     upto are replayed in registers.  Nothing but `out` is written: duplicates in idx and concurrent readers are free.
+ *   - Sparse step: sorted_rows int32 [n] = the step's row ids ascending (wr_rows_sparse_keys, then a STABLE sort by key), perm
+ *     int64 [n] = the position of every entry in the concatenation of the step's lookups, src [n, D] the gradient rows in that
+ *     order.  Per run of equal rows, one wave: g = src[perm[q],:] summed over the run in ascending q starting from +0 (the
+ *     association of wr_scatter_add_rows into a zero table), replay of the row through step - 1, the step itself with g, then
+ *     w / m / v and last_step[row] = step are written.  A run of padding_idx contributes no gradient but takes the step with
+ *     g = 0 (SASRec gathers row 0 at every padded position: the row stays current).  wr_sgd_rows_sparse: l2 == 0: w -= lr*g on
+ *     the rows with a gradient, last_step unused (may be NULL); l2 != 0: missed decays, then g' = g + l2*w; w -= lr*g'.
+ *   - Same element arithmetic and order as wr_adam_dense / wr_sgd_dense: after wr_*_catchup_all the tables hold the bits of
+ *     "zero table, wr_scatter_add_rows, wr_*_dense" repeated step by step.  One writer per row, no float atomics, no [n_rows, D]
+ *     temporary.  Rows no step names are advanced by wr_*_catchup_all, whole or on a window (pointers offset to its first row).
+ *   - idx int64; 0 <= n < 2^31; upto / step < n_consts.  An id outside [0, n_rows) is never dereferenced: the gather writes a
+ *     zero row for it, wr_rows_sparse_keys gives it the key n_rows (sorted last, never applied); a perm entry outside [0, n)
+ *     contributes nothing.  err_word (int32 on the device, may be NULL; the caller clears and reads it): bit 1 a row id
+ *     outside the table, bit 2 a perm entry outside [0, n).  No workspace, no allocation, no host round trip. */
+int32_t wr_gather_rows_lazy(const float *tab, const float *exp_avg, const float *exp_avg_sq, const int32_t *last_step,
+                            int64_t n_rows, int32_t D, const int64_t *idx, int64_t n, int64_t upto, const float *consts,
+                            int64_t n_consts, float l2, float beta1, float beta2, float eps, float *out, int32_t *err_word,
+                            void *stream);
+int32_t wr_gather_rows_lazy_sgd(const float *tab, const int32_t *last_step, int64_t n_rows, int32_t D, const int64_t *idx,
+                                int64_t n, int64_t upto, float lr, float l2, float *out, int32_t *err_word, void *stream);
+int32_t wr_rows_sparse_keys(const int64_t *idx, int64_t n, int64_t n_rows, int32_t *keys, int32_t *err_word, void *stream);
+int32_t wr_adam_rows_sparse(float *tab, float *exp_avg, float *exp_avg_sq, int32_t *last_step, int64_t n_rows, int32_t D,
+                            const int32_t *sorted_rows, const int64_t *perm, int64_t n, const float *src, int64_t padding_idx,
+                            int64_t adam_step, const float *consts, int64_t n_consts, float l2, float beta1, float beta2,
+                            float eps, int32_t *err_word, void *stream);
+int32_t wr_sgd_rows_sparse(float *tab, int32_t *last_step, int64_t n_rows, int32_t D, const int32_t *sorted_rows,
+                           const int64_t *perm, int64_t n, const float *src, int64_t padding_idx, int64_t step, float lr,
+                           float l2, int32_t *err_word, void *stream);
+
 /* LightGCN.predict's per-batch tail in two launches (src/models/general/LightGCN.py:156-175, src/utils/loss.py:37-39,94-98):
  *   loss[0] = mean_b( -log(1e-10 + sigmoid(<Ua[u_b], Ia[p_b]> - <Ua[u_b], Ia[n_b]>)) )
  *             + reg_weight * (||U0[u]||_F + ||I0[p]||_F + ||I0[n]||_F) / B

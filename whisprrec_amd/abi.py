@@ -218,6 +218,13 @@ SIGNATURES = {
     "wr_seq_augment_supported": (c_i32, [c_i32, c_i32, c_i32]),
     "wr_seq_augment": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_vp, c_i64, c_i64, c_i32, c_i32, ctypes.c_uint64, ctypes.c_uint64, c_vp,
                                c_vp, c_vp, c_vp]),
+    "wr_gather_rows_lazy": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_vp, c_i64, c_i64, c_vp, c_i64, c_f32, c_f32, c_f32,
+                                    c_f32, c_vp, c_vp, c_vp]),
+    "wr_gather_rows_lazy_sgd": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_vp, c_i64, c_i64, c_f32, c_f32, c_vp, c_vp, c_vp]),
+    "wr_rows_sparse_keys": (c_i32, [c_vp, c_i64, c_i64, c_vp, c_vp, c_vp]),
+    "wr_adam_rows_sparse": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64,
+                                    c_f32, c_f32, c_f32, c_f32, c_vp, c_vp]),
+    "wr_sgd_rows_sparse": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_f32, c_f32, c_vp, c_vp]),
     "wr_lightgcn_loss_workspace_bytes": (c_i64, [c_i64]),
     "wr_lightgcn_loss": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_vp, c_vp, c_vp, c_i64, c_f32, c_vp, c_vp, c_vp,
                                  c_i64, c_vp]),

@@ -30,7 +30,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import hip_ops, host
-from .sasrec import HipEmbedding, _Block
+from .sasrec import EmbLazyMixin, HipEmbedding, _Block
 
 
 def _xavier_uniform_all(module):
@@ -83,7 +83,7 @@ class BERT4RecEncoder(nn.Module):
 
 
 def make_contrarec(sequential_model_cls):
-    class ContraRec(sequential_model_cls):
+    class ContraRec(EmbLazyMixin, sequential_model_cls):
         reader = "SeqReader"
         runner = "BaseRunner"
         extra_log_args = ["gamma", "num_neg", "batch_size", "ccc_temp"]
@@ -106,6 +106,7 @@ def make_contrarec(sequential_model_cls):
                                 help="1: the two augmented views of every batch are drawn on the device and the model trains "
                                      "through HipRunner's batch loop; the views follow the reference's distribution and are keyed "
                                      "by --random_seed, but are not NumPy's stream.  0: the reference's per-sample DataLoader loop.")
+            EmbLazyMixin.add_emb_lazy_arg(parser)
             return sequential_model_cls.parse_model_args(parser)
 
         def __init__(self, args, corpus):
@@ -131,6 +132,7 @@ def make_contrarec(sequential_model_cls):
                 else:
                     logging.warning("--aug_native 1: the view builder does not take history_max=%s beta_a=%s beta_b=%s; keeping "
                                     "the host path", self.max_his, self.beta_a, self.beta_b)
+            self._install_emb_lazy(args, self.item_embeddings)
 
         # ------------------------------------------------------------------------------------ native paths
         def _use_block_native(self, T):
@@ -219,6 +221,7 @@ def make_contrarec(sequential_model_cls):
 
         def full_predict(self, feed_dict):
             # all item_num + 1 rows: the reference ranks the mask-token column too (ContraRec.py:98-104)
+            self._sync_tables()
             return torch.matmul(self.forward(feed_dict), self.item_embeddings.weight.t())
 
         # The query protocol of HipRunner's device evaluation (--seq_eval_native 1) and recommend_rows, as SASRec's.
@@ -235,6 +238,7 @@ def make_contrarec(sequential_model_cls):
 
         def eval_items(self):
             """[item_num + 1, D] item side of the scores: full_predict's second operand, the mask-token row included"""
+            self._sync_tables()
             return self.item_embeddings.weight
 
         class Dataset(sequential_model_cls.Dataset):

@@ -396,6 +396,24 @@ __device__ __forceinline__ void adam_elem_zero_grad(float &w, float &m, float &v
     w = fmaf(-step_size, m * __builtin_amdgcn_rcpf(denom), w);
 }
 
+// Steps from+1 .. upto of one element with a zero gradient — the replay of the lazy optimizers (wr_lazy.hip, wr_rowopt.hip),
+// which must agree bit for bit.  c2[s] = {step_size, 1/sqrt(bias_correction2)} of step s (wr_adam_consts); four steps per
+// trip: their (wave-uniform) constants are fetched together.
+template <bool L2>
+__device__ __forceinline__ void adam_replay_elem(float &w, float &m, float &v, int from, int upto, const float2 *__restrict__ c2,
+                                                 float l2, float b1, float b2, float eps) {
+    auto replay = [&](float2 k) {   // one gradient-free step
+        if (L2) adam_elem<true>(w, m, v, 0.f, l2, b1, b2, eps, k.x, k.y);
+        else adam_elem_zero_grad(w, m, v, b1, b2, eps, k.x, k.y);
+    };
+    int s = from + 1;
+    for (; s + 3 <= upto; s += 4) {
+        const float2 k0 = c2[s], k1 = c2[s + 1], k2 = c2[s + 2], k3 = c2[s + 3];
+        replay(k0); replay(k1); replay(k2); replay(k3);
+    }
+    for (; s <= upto; ++s) replay(c2[s]);
+}
+
 // Host side of the same step: step_size = lr/(1-beta1^t), 1/sqrt(1-beta2^t), in double as torch computes the bias
 // corrections for a python-number step, rounded to fp32 once.
 static inline void adam_step_consts(int64_t t, float lr, float beta1, float beta2, float *step_size, float *inv_bc2_sqrt) {

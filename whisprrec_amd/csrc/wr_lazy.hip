@@ -32,10 +32,6 @@ __device__ __forceinline__ void adam_rows(float *__restrict__ w, float *__restri
                                           const float *__restrict__ grad, const float *__restrict__ consts, float l2, float b1,
                                           float b2, float eps, int lane) {
     const float2 *__restrict__ c2 = reinterpret_cast<const float2 *>(consts);
-    auto replay = [&](float &ww, float &mm, float &vv, float2 k) {   // one gradient-free step
-        if (L2) adam_elem<true>(ww, mm, vv, 0.f, l2, b1, b2, eps, k.x, k.y);
-        else adam_elem_zero_grad(ww, mm, vv, b1, b2, eps, k.x, k.y);
-    };
     int64_t rows[R];
     int from[R];
 #pragma unroll
@@ -57,13 +53,7 @@ __device__ __forceinline__ void adam_rows(float *__restrict__ w, float *__restri
 #pragma unroll
         for (int j = 0; j < R; ++j) {
             if (rows[j] < 0) continue;
-            int s = from[j] + 1;
-            for (; s + 3 <= upto; s += 4) {   // four steps per trip: their (wave-uniform) constants are fetched together
-                const float2 k0 = c2[s], k1 = c2[s + 1], k2 = c2[s + 2], k3 = c2[s + 3];
-                replay(ww[j], mm[j], vv[j], k0); replay(ww[j], mm[j], vv[j], k1);
-                replay(ww[j], mm[j], vv[j], k2); replay(ww[j], mm[j], vv[j], k3);
-            }
-            for (; s <= upto; ++s) replay(ww[j], mm[j], vv[j], c2[s]);
+            adam_replay_elem<L2>(ww[j], mm[j], vv[j], from[j], upto, c2, l2, b1, b2, eps);
             if (grad != nullptr) adam_elem<L2>(ww[j], mm[j], vv[j], gg[j], l2, b1, b2, eps, c2[upto + 1].x, c2[upto + 1].y);
             const int64_t at = rows[j] * (int64_t)D + e;
             w[at] = ww[j]; m[at] = mm[j]; v[at] = vv[j];

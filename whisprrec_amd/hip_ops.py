@@ -2410,6 +2410,238 @@ def scatter_add_rows(grad, idx, src, padding_idx=-1, alpha=1.0):
     return grad
 
 
+# ----------------------------------------------------------------------------------------------- row-lazy optimizers (K22)
+ROW_ERR_ID, ROW_ERR_PERM = 1, 2          # bits of the kernels' device error word
+
+
+def _raise_row_errors(err, what):
+    """one read of a device error word of the K22 kernels; clears it and raises IndexError if a bit is set"""
+    word = int(err.item())
+    if word:
+        err.zero_()
+        raise IndexError("%s: %s" % (what, " and ".join(
+            t for bit, t in ((ROW_ERR_ID, "a row id outside the table"), (ROW_ERR_PERM, "a position outside the step's rows"))
+            if word & bit)))
+
+
+def gather_rows_lazy(tab, exp_avg, exp_avg_sq, last, idx, upto, consts, l2=0.0, beta1=0.9, beta2=0.999, eps=1e-8, err_word=None):
+    """out[..., :] = row idx[...] of `tab` as dense Adam holds it after step `upto` (wr_gather_rows_lazy): the steps
+    last[row]+1 .. upto are replayed in registers, nothing but `out` is written.  err_word given: ids outside the table set
+    bit 1 there (their output rows are zeros) and the caller reads it; None: checked here, IndexError."""
+    for t, nm in ((tab, "tab"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
+        _req(t, torch.float32, nm, 2)
+    _req(last, torch.int32, "last", 1)
+    flat = _idx64(idx.reshape(-1), "idx")
+    out = torch.empty((flat.numel(), tab.shape[1]), dtype=torch.float32, device=tab.device)
+    err = err_word if err_word is not None else torch.zeros(1, dtype=torch.int32, device=tab.device)
+    abi.check(abi.lib().wr_gather_rows_lazy(_p(tab), _p(exp_avg), _p(exp_avg_sq), _p(last), tab.shape[0], tab.shape[1], _p(flat),
+                                            flat.numel(), int(upto), _p(consts), consts.numel() // 2, l2, beta1, beta2, eps,
+                                            _p(out), _p(err), _stream()), "wr_gather_rows_lazy")
+    if err_word is None:
+        _raise_row_errors(err, "gather_rows_lazy")
+    return out.reshape(tuple(idx.shape) + (tab.shape[1],))
+
+
+def gather_rows_lazy_sgd(tab, last, idx, upto, lr, l2, err_word=None):
+    """gather_rows_lazy for SGD with weight decay: the missed decays w <- w - lr*l2*w are replayed (wr_gather_rows_lazy_sgd)"""
+    _req(tab, torch.float32, "tab", 2)
+    _req(last, torch.int32, "last", 1)
+    flat = _idx64(idx.reshape(-1), "idx")
+    out = torch.empty((flat.numel(), tab.shape[1]), dtype=torch.float32, device=tab.device)
+    err = err_word if err_word is not None else torch.zeros(1, dtype=torch.int32, device=tab.device)
+    abi.check(abi.lib().wr_gather_rows_lazy_sgd(_p(tab), _p(last), tab.shape[0], tab.shape[1], _p(flat), flat.numel(), int(upto),
+                                                lr, l2, _p(out), _p(err), _stream()), "wr_gather_rows_lazy_sgd")
+    if err_word is None:
+        _raise_row_errors(err, "gather_rows_lazy_sgd")
+    return out.reshape(tuple(idx.shape) + (tab.shape[1],))
+
+
+def rows_sparse_order(idx, n_rows, err_word=None):
+    """(row, position) order of a step's positions: -> (sorted_rows int32 [n], perm int64 [n]).  The keys come from
+    wr_rows_sparse_keys (ids outside the table: key n_rows, bit 1 of the error word); the ordering itself is a stable
+    torch.sort of the 32-bit keys ("Row-lazy item table": the library's sorting stages are private to
+    wr_scatter_add_rows and produce its tile / plan layouts, not one sorted list)."""
+    flat = _idx64(idx.reshape(-1), "idx")
+    keys = torch.empty(flat.numel(), dtype=torch.int32, device=flat.device)
+    abi.check(abi.lib().wr_rows_sparse_keys(_p(flat), flat.numel(), int(n_rows), _p(keys), _p(err_word), _stream()),
+              "wr_rows_sparse_keys")
+    if flat.numel() == 0:
+        return keys, torch.empty(0, dtype=torch.int64, device=flat.device)
+    return torch.sort(keys, stable=True)
+
+
+def adam_rows_sparse(tab, exp_avg, exp_avg_sq, last, sorted_rows, perm, src, adam_step, consts, l2=0.0, beta1=0.9, beta2=0.999,
+                     eps=1e-8, padding_idx=-1, err_word=None):
+    """torch.optim.Adam's step `adam_step` on the rows of sorted_rows only (wr_adam_rows_sparse): per run of equal rows the sum
+    of src[perm[q]] in ascending q, the row's missed zero-gradient steps, the step; last[row] = adam_step.  In place."""
+    for t, nm in ((tab, "tab"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
+        _req(t, torch.float32, nm, 2)
+    _req(last, torch.int32, "last", 1)
+    _req(sorted_rows, torch.int32, "sorted_rows", 1)
+    _req(perm, torch.int64, "perm", 1)
+    n = sorted_rows.numel()
+    src2 = _req(src.reshape(-1, tab.shape[1]), torch.float32, "src", 2)
+    if perm.numel() != n or src2.shape[0] != n:
+        raise ValueError("adam_rows_sparse: sorted_rows, perm and src must hold the same number of positions")
+    abi.check(abi.lib().wr_adam_rows_sparse(_p(tab), _p(exp_avg), _p(exp_avg_sq), _p(last), tab.shape[0], tab.shape[1],
+                                            _p(sorted_rows), _p(perm), n, _p(src2), int(padding_idx), int(adam_step), _p(consts),
+                                            consts.numel() // 2, l2, beta1, beta2, eps, _p(err_word), _stream()),
+              "wr_adam_rows_sparse")
+
+
+def sgd_rows_sparse(tab, last, sorted_rows, perm, src, step, lr, l2=0.0, padding_idx=-1, err_word=None):
+    """torch.optim.SGD's step on the rows of sorted_rows only (wr_sgd_rows_sparse); last: int32 [n_rows], or None when l2 == 0"""
+    _req(tab, torch.float32, "tab", 2)
+    if last is not None:
+        _req(last, torch.int32, "last", 1)
+    elif l2 != 0.0:
+        raise ValueError("sgd_rows_sparse: weight decay needs the rows' last steps")
+    _req(sorted_rows, torch.int32, "sorted_rows", 1)
+    _req(perm, torch.int64, "perm", 1)
+    n = sorted_rows.numel()
+    src2 = _req(src.reshape(-1, tab.shape[1]), torch.float32, "src", 2)
+    if perm.numel() != n or src2.shape[0] != n:
+        raise ValueError("sgd_rows_sparse: sorted_rows, perm and src must hold the same number of positions")
+    abi.check(abi.lib().wr_sgd_rows_sparse(_p(tab), _p(last), tab.shape[0], tab.shape[1], _p(sorted_rows), _p(perm), n, _p(src2),
+                                           int(padding_idx), int(step), lr, l2, _p(err_word), _stream()), "wr_sgd_rows_sparse")
+
+
+class RowLazyTable:
+    """torch.optim.Adam / SGD(weight_decay) on ONE table whose gradient arrives as (index, gradient row) pairs — the item table of
+    the sequential models (include/whisprrec_hip.h, K22).  Every row carries the number of the last optimizer step applied to
+    it; ``gather`` returns rows as of the current step without writing anything, ``step`` moves the rows of the step only,
+    ``flush`` brings all rows up to date — call it before anything else reads ``weight``.  After a flush, weight and moments
+    hold the bits of "zero table, scatter_add_rows, adam_dense / sgd_dense" repeated step by step."""
+
+    MAX_LAG, LAG_MIN_GAP = LazyOptimizerState.MAX_LAG, LazyOptimizerState.LAG_MIN_GAP
+
+    def __init__(self, weight, name, lr, l2, betas=(0.9, 0.999), eps=1e-8, max_lag=None, padding_idx=-1):
+        """max_lag as for LazyOptimizerState: None = MAX_LAG when a row misses more than LAG_MIN_GAP steps between two uses on
+        average (rows / positions of the step), 0 = unbounded, n = before every step a rotating window of rows / n rows is
+        brought up to date (wr_adam_catchup_all / wr_sgd_catchup_all on the window), so that no row ever lags more than n."""
+        if name not in ("SGD", "Adam"):
+            raise ValueError(name)
+        _req(weight, torch.float32, "weight", 2)
+        self.w, self.name, self.lr, self.l2 = weight, name, float(lr), float(l2)
+        self.betas, self.eps = (float(betas[0]), float(betas[1])), float(eps)
+        self.max_lag = max_lag if max_lag is None else int(max_lag)
+        self.padding_idx = int(padding_idx)
+        self.t = 0                               # optimizer steps taken
+        self.flushed_at = 0
+        self._sweep = 0                          # first row of the next window
+        dev = weight.device
+        self.err = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.stateful = name == "Adam" or self.l2 != 0.0      # SGD without decay: untouched rows never move
+        self.m = self.v = self.last = self.consts = None
+        if self.stateful:
+            self.last = torch.zeros(weight.shape[0], dtype=torch.int32, device=dev)
+        if name == "Adam":
+            self.m, self.v = torch.zeros_like(weight), torch.zeros_like(weight)
+            self._grow_consts(4096)
+
+    def _grow_consts(self, n):
+        host = torch.empty(2 * n, dtype=torch.float32)
+        abi.check(abi.lib().wr_adam_consts(0, n, self.lr, self.betas[0], self.betas[1], host.data_ptr()), "wr_adam_consts")
+        self.consts = host.to(self.w.device)
+        self.n_consts = n
+
+    def check(self):
+        """one read of the device error word that unchecked gathers and steps leave their findings in"""
+        _raise_row_errors(self.err, "RowLazyTable")
+
+    def gather(self, idx, check=True):
+        """rows idx[...] as of step t.  check: ids outside the table raise IndexError here (one device read); else they come
+        back as zero rows and the finding waits in the error word for check() / flush()."""
+        if not self.stateful:
+            if check:
+                flat = idx.reshape(-1)
+                if flat.numel() and (int(flat.min()) < 0 or int(flat.max()) >= self.w.shape[0]):
+                    raise IndexError("RowLazyTable: a row id outside the table")
+            return gather_rows(self.w, idx)
+        if self.name == "Adam":
+            out = gather_rows_lazy(self.w, self.m, self.v, self.last, idx, self.t, self.consts, self.l2, *self.betas, self.eps,
+                                   err_word=self.err)
+        else:
+            out = gather_rows_lazy_sgd(self.w, self.last, idx, self.t, self.lr, self.l2, err_word=self.err)
+        if check:
+            self.check()
+        return out
+
+    def _catchup(self, lo, count, upto):
+        """rows [lo, lo + count) up to step `upto` (zero gradients)"""
+        L, D = abi.lib(), self.w.shape[1]
+        if self.name == "Adam":
+            abi.check(L.wr_adam_catchup_all(_p(self.w[lo:]), _p(self.m[lo:]), _p(self.v[lo:]), _p(self.last[lo:]), count, D, upto,
+                                            _p(self.consts), self.n_consts, self.l2, self.betas[0], self.betas[1], self.eps,
+                                            _stream()), "wr_adam_catchup_all")
+        else:
+            abi.check(L.wr_sgd_catchup_all(_p(self.w[lo:]), _p(self.last[lo:]), count, D, upto, self.lr, self.l2, _stream()),
+                      "wr_sgd_catchup_all")
+
+    def _lag(self, n_positions):
+        if self.max_lag is None:
+            return self.MAX_LAG if self.w.shape[0] / float(max(n_positions, 1)) > self.LAG_MIN_GAP else 0
+        return self.max_lag
+
+    def _turn_window(self, lag, upto):
+        """the rotating window of ceil(rows / lag) rows -> step `upto`, in up to two pieces across the wrap-around"""
+        n_rows = self.w.shape[0]
+        left, lo = min((n_rows + lag - 1) // lag, n_rows), self._sweep % n_rows
+        while left > 0:
+            c = min(left, n_rows - lo)
+            self._catchup(lo, c, upto)
+            lo, left = (lo + c) % n_rows, left - c
+        self._sweep = lo
+
+    def step(self, idx_list, grad_list, check=True):
+        """optimizer step t + 1 with the gradient rows grad_list[i][k, :] of the rows idx_list[i][k]: the lists are concatenated
+        in list order (the order of the forward lookups), brought into (row, position) order, the window is turned and the
+        step's rows are moved.  check: an id outside the table raises IndexError before anything is written."""
+        if len(idx_list) != len(grad_list):
+            raise ValueError("RowLazyTable.step: as many index tensors as gradient tensors")
+        D = self.w.shape[1]
+        idx = [_idx64(i.reshape(-1), "idx") for i in idx_list]
+        grads = [g.reshape(-1, D) for g in grad_list]
+        for i, g in zip(idx, grads):
+            if g.shape[0] != i.numel():
+                raise ValueError("RowLazyTable.step: %d gradient rows for %d indices" % (g.shape[0], i.numel()))
+        n = sum(i.numel() for i in idx)
+        if n:
+            cat = torch.cat(idx) if len(idx) > 1 else idx[0]
+            rows, perm = rows_sparse_order(cat, self.w.shape[0], err_word=self.err)
+            if check:
+                self.check()
+            src = _req((torch.cat(grads) if len(grads) > 1 else grads[0]).contiguous(), torch.float32, "grad", 2)
+        t = self.t + 1
+        if self.stateful:
+            if self.name == "Adam" and t >= self.n_consts:
+                self._grow_consts(2 * self.n_consts)
+            lag = self._lag(n)
+            if lag > 0 and t > 1:
+                self._turn_window(lag, t - 1)
+        if n:
+            if self.name == "Adam":
+                adam_rows_sparse(self.w, self.m, self.v, self.last, rows, perm, src, t, self.consts, self.l2, *self.betas, self.eps,
+                                 padding_idx=self.padding_idx, err_word=self.err)
+            else:
+                sgd_rows_sparse(self.w, self.last, rows, perm, src, t, self.lr, self.l2, padding_idx=self.padding_idx,
+                                err_word=self.err)
+        self.t = t
+
+    def flush(self):
+        """every row up to step t: weight (and the moments) are then what the dense optimizer holds.  A no-op when nothing
+        happened since the last flush.  Also where the findings of unchecked calls are raised."""
+        if self.flushed_at != self.t:
+            if self.stateful:
+                self._catchup(0, self.w.shape[0], self.t)
+            self.flushed_at = self.t
+            self.check()
+
+    def behind(self):
+        """steps the most outdated row lags behind (one device read)"""
+        return self.t - int(self.last.min()) if self.stateful else 0
+
+
 class ScatterPlan:
     """Row plan of several scatter-adds whose indices are known ahead (wr_scatter.hip): idx [n_segments, seg_stride] int64
     (segment s uses its first seg_len[s] positions; seg_len int32 on the device, or None = all).  ``apply(table, s, n, src,

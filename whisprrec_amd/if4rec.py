@@ -37,7 +37,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import hip_ops, host
-from .sasrec import HipEmbedding, _Block, _xavier_normal_all
+from .sasrec import EmbLazyMixin, HipEmbedding, _Block, _xavier_normal_all
 
 
 def interest_pool_torch(his_pos, valid, W1, W2):
@@ -57,7 +57,7 @@ def interest_pool_torch(his_pos, valid, W1, W2):
 
 
 def make_if4rec(sequential_model_cls):
-    class IF4Rec(sequential_model_cls):
+    class IF4Rec(EmbLazyMixin, sequential_model_cls):
         reader = "SeqReader"
         runner = "BaseRunner"
         extra_log_args = ["emb_size", "attn_size", "K", "encoder_layer", "n_head", "encoder_dropout", "add_pos", "add_multi"]
@@ -78,6 +78,7 @@ def make_if4rec(sequential_model_cls):
             parser.add_argument("--block_native", type=int, default=0, choices=[0, 1],
                                 help="1: each block over the interest tokens by the fused HIP kernels (n_head in {1, 2, 4}); "
                                      "0: torch ops + autograd.")
+            EmbLazyMixin.add_emb_lazy_arg(parser)
             return sequential_model_cls.parse_model_args(parser)
 
         def __init__(self, args, corpus):
@@ -103,6 +104,9 @@ def make_if4rec(sequential_model_cls):
             self._block_calls = 0            # one dropout stream per training step and layer
             self._id_err = None              # device error word of the history ids, read by check_history_ids()
             self._key_len = None             # [B] tensor of K: every interest token is a key
+            # the pooling kernels read the table's rows themselves (wr_if4rec.hip): they would see rows that lag
+            self._install_emb_lazy(args, self.i_embeddings, blocked="--interest_native 1 reads the item table inside the pooling "
+                                   "kernels" if self.interest_native else None)
 
         n_interests = property(lambda self: self.K)
 
@@ -185,6 +189,7 @@ def make_if4rec(sequential_model_cls):
             return -torch.log(1e-10 + torch.sigmoid(prediction[:, :1] - prediction[:, 1:])).mean()
 
         def full_predict(self, feed_dict):
+            self._sync_tables()
             return torch.matmul(self.forward(feed_dict), self.i_embeddings.weight.t()).max(1)[0]
 
         # The interest protocol of HipRunner's device evaluation (--seq_eval_native 1): a model whose score of row e against
@@ -202,6 +207,7 @@ def make_if4rec(sequential_model_cls):
 
         def eval_items(self):
             """[item_num, D] item side of the scores: full_predict's second operand"""
+            self._sync_tables()
             return self.i_embeddings.weight
 
     IF4Rec.__qualname__ = "IF4Rec"

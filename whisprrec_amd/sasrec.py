@@ -8,6 +8,10 @@ interchange, and has two paths.  ``--block_native 0`` (default): stock PyTorch-R
 each block is one call of ``hip_ops.sasrec_block`` (wr_sasblock.hip, K13) — two launches forward, two backward, in training
 and evaluation alike; its dropout mask is the kernel's own counter-based generator, seeded per step and per layer from
 ``--random_seed``.  A shape the kernels do not take is logged once and keeps the stock path.
+``--emb_lazy 1`` (SASRec, ContraRec, IF4Rec; Adam and SGD): the item table gets no dense gradient.  ``HipEmbedding`` reads rows
+through ``hip_ops.RowLazyTable.gather`` (wr_rowopt.hip, K22: the optimizer steps a row has missed are replayed on the way, nothing
+is written), its backward hands (idx, grad_out) to ``RowLazyOptimizer``, which advances the table row by row exactly as the dense
+optimizer would and leaves every other parameter to ``torch.optim``; ``EmbLazyMixin`` flushes before anything else reads the table.
 """
 import logging
 
@@ -46,9 +50,139 @@ class HipEmbedding(nn.Module):
         if padding_idx is not None:
             with torch.no_grad():
                 self.weight[padding_idx].fill_(0)
+        self._lazy = None           # a RowLazyOptimizer: the weight's optimizer state is advanced row by row (--emb_lazy 1)
+        self._pending = []           # (lookup number, idx, grad_out) of the step's lookups whose backward has run
+        self._lookups = 0            # training lookups since zero_grad
+        self._marker = None
+
+    def bind_lazy(self, optimizer):
+        """lazy mode: forward reads rows as of the optimizer's current step (RowLazyTable.gather), backward hands (idx,
+        grad_out) to the optimizer's sparse step instead of building a [num_embeddings, D] gradient; weight.grad stays None"""
+        self._lazy = optimizer
 
     def forward(self, idx):
-        return _GatherRows.apply(self.weight, idx, self.padding_idx)
+        if self._lazy is None:
+            return _GatherRows.apply(self.weight, idx, self.padding_idx)
+        if not (self.training and torch.is_grad_enabled()):
+            return self._lazy.table().gather(idx, check=False)     # nothing is recorded
+        if self._marker is None or self._marker.device != self.weight.device:
+            # autograd calls a backward only below an input that requires grad; the weight must not be that input (it would
+            # be handed a dense gradient), so a scalar stands in for it (bprmf._DeferredBprLoss's trick)
+            self._marker = torch.zeros((), device=self.weight.device, requires_grad=True)
+        self._lookups += 1
+        return _LazyGatherRows.apply(self._marker, idx, self, self._lookups)
+
+
+class _LazyGatherRows(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, marker, idx, module, number):
+        ctx.save_for_backward(idx)
+        ctx.module, ctx.number = module, number
+        return module._lazy.table().gather(idx, check=False)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        (idx,) = ctx.saved_tensors
+        ctx.module._pending.append((ctx.number, idx, grad_out.contiguous()))
+        return None, None, None, None
+
+
+class RowLazyOptimizer:
+    """Duck-types what the runners need from ``model.optimizer`` (``zero_grad`` / ``step``, as bprmf.FusedOptimizer does) for a
+    model whose item table is a lazy ``HipEmbedding``: every other parameter is stepped by ``torch.optim.<name>(lr,
+    weight_decay=l2)``, the table by ``hip_ops.RowLazyTable`` — row by row, exactly as dense Adam / SGD would advance it, from
+    the (idx, grad_out) pairs the lookups' backward recorded, in the order of the forward lookups."""
+
+    @staticmethod
+    def supports(name):
+        return name in ("SGD", "Adam")
+
+    def __init__(self, model, emb, name, lr, l2, max_lag=None):
+        if not self.supports(name):
+            raise ValueError("RowLazyOptimizer supports SGD and Adam, got %r" % (name,))
+        self.emb, self.name, self.lr, self.l2, self.max_lag = emb, name, float(lr), float(l2), max_lag
+        others = [p for p in model.parameters() if p is not emb.weight]
+        self.inner = getattr(torch.optim, name)(others, lr=self.lr, weight_decay=self.l2)
+        self._table = None
+        emb.bind_lazy(self)
+
+    param_groups = property(lambda self: self.inner.param_groups)
+
+    def table(self):
+        """the RowLazyTable of the weight's present storage (models are built on the host and moved afterwards)"""
+        w = self.emb.weight.data
+        if self._table is None or self._table.w.data_ptr() != w.data_ptr():
+            if self._table is not None and self._table.t > 0:
+                raise RuntimeError("the embedding table was re-allocated after optimizer steps had been taken")
+            self._table = hip_ops.RowLazyTable(w, self.name, self.lr, self.l2, max_lag=self.max_lag,
+                                               padding_idx=self.emb.padding_idx)
+        return self._table
+
+    def zero_grad(self, set_to_none=True):
+        self.inner.zero_grad(set_to_none=set_to_none)
+        self.emb._pending.clear()
+        self.emb._lookups = 0
+
+    @torch.no_grad()
+    def step(self):
+        pending = sorted(self.emb._pending, key=lambda e: e[0])
+        if not pending:
+            raise RuntimeError("optimizer.step() without a preceding training predict() / backward(): no lookup of the lazy "
+                               "table recorded a gradient")
+        self.table().step([e[1] for e in pending], [e[2] for e in pending], check=False)
+        self.inner.step()
+        self.emb._pending.clear()
+        self.emb._lookups = 0
+
+    def flush(self):
+        """every row of the table up to the current step; called by the model before anything but a training step reads it"""
+        if self._table is not None:
+            self._table.flush()
+
+
+class EmbLazyMixin:
+    """``--emb_lazy`` for a model whose item table is a ``HipEmbedding``: the flag, the pre-installed optimizer (the runners
+    build one only while ``model.optimizer`` is None, as for BPRMF) and the flushes before anything but a training step reads
+    the table (the pattern of bprmf.BPRMF._sync_tables).  With the flag off every method here falls through."""
+
+    @staticmethod
+    def add_emb_lazy_arg(parser):
+        parser.add_argument("--emb_lazy", type=int, default=0, choices=[0, 1],
+                            help="1: the item table gets no dense gradient; its Adam / SGD state is advanced row by row, exactly "
+                                 "as the dense optimizer would (other parameters keep torch.optim).  0: dense gradient + torch.optim.")
+
+    def _install_emb_lazy(self, args, emb, blocked=None):
+        """blocked: why this configuration cannot take the lazy table (logged once), or None"""
+        self.emb_lazy = False
+        if not int(getattr(args, "emb_lazy", 0)):
+            return
+        name = getattr(args, "optimizer", None)
+        if blocked is None and not (RowLazyOptimizer.supports(name) and hasattr(args, "lr")):
+            blocked = "--optimizer %s is not SGD or Adam" % (name,)
+        if blocked is not None:
+            logging.warning("--emb_lazy 1: %s; keeping the dense gradient and torch.optim", blocked)
+            return
+        self.optimizer = RowLazyOptimizer(self, emb, name, args.lr, getattr(args, "l2", 0.0))
+        self.emb_lazy = True
+
+    def _sync_tables(self):
+        """lazy rows -> current (a no-op otherwise); every reader of the item table outside a training step calls it"""
+        opt = getattr(self, "optimizer", None)
+        if isinstance(opt, RowLazyOptimizer):
+            opt.flush()
+
+    def train(self, mode=True):
+        if not mode:
+            self._sync_tables()           # model.eval() precedes every evaluation
+        return super().train(mode)
+
+    def state_dict(self, *a, **kw):
+        self._sync_tables()
+        return super().state_dict(*a, **kw)
+
+    def load_state_dict(self, *a, **kw):
+        self._sync_tables()               # pending replays belong to the old weights
+        return super().load_state_dict(*a, **kw)
 
 
 class _Attention(nn.Module):
@@ -104,7 +238,7 @@ def _xavier_normal_all(module):
 
 
 def make_sasrec(sequential_model_cls):
-    class SASRec(sequential_model_cls):
+    class SASRec(EmbLazyMixin, sequential_model_cls):
         reader = "SeqReader"
         runner = "BaseRunner"
         extra_log_args = ["emb_size", "num_layers", "num_heads"]
@@ -117,6 +251,7 @@ def make_sasrec(sequential_model_cls):
             parser.add_argument("--dropout", type=float, default=0.1, help="Dropout probability.")
             parser.add_argument("--block_native", type=int, default=0, choices=[0, 1],
                                 help="1: each transformer block by the fused HIP kernels (forward and backward); 0: torch ops + autograd.")
+            EmbLazyMixin.add_emb_lazy_arg(parser)
             return sequential_model_cls.parse_model_args(parser)
 
         def __init__(self, args, corpus):
@@ -132,6 +267,7 @@ def make_sasrec(sequential_model_cls):
             self._block_native_ok = {}   # per history length, decided at its first batch: the library says what it takes
             self._block_seed = int(getattr(args, "random_seed", 0)) * 0x9E3779B97F4A7C15
             self._block_calls = 0        # one dropout stream per training step and layer
+            self._install_emb_lazy(args, self.item_embedding)
 
         def _use_block_native(self, T):
             if not self.block_native:
@@ -170,6 +306,7 @@ def make_sasrec(sequential_model_cls):
             return -torch.log(1e-10 + torch.sigmoid(pos - neg)).mean()                   # BPRLoss, loss.py:38
 
         def full_predict(self, feed_dict):
+            self._sync_tables()
             return torch.matmul(self.forward(feed_dict), self.item_embedding.weight.t())
 
         # The query protocol of HipRunner's device evaluation (--seq_eval_native 1) and recommend_rows: a model whose score
@@ -187,6 +324,7 @@ def make_sasrec(sequential_model_cls):
 
         def eval_items(self):
             """[n_items, D] item side of the scores: full_predict's second operand"""
+            self._sync_tables()
             return self.item_embedding.weight
 
     SASRec.__qualname__ = "SASRec"
