@@ -998,7 +998,36 @@ int32_t wr_rank_eval_multi(const float *query_mat, int64_t n_query_rows, const f
                            const int64_t *mask_ptr, const int32_t *mask_idx, int32_t *rank, float *target_score, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------
- * K20  SGL's augmented graph views (src/utils/augmentor.py:33-111, csr2tensor of src/models/general/SGL.py:105-146) built on
+ * K23  Top-K recommendation with KQ query vectors per row — multi-interest models (IF4Rec), the selection side of K19:
+ *   score(e, j) = max_{q < KQ} <query_mat[e KQ + q], item_tab[j]>                              query_mat [n KQ, D]
+ *   out         = the k unmasked items of every evaluation row e with the largest score(e, j)
+ *   - Scores: each <.,.> is the fp32 k-ordered chain of v_mfma_f32_32x32x2_f32; a returned score is bitwise wr_rank_eval_multi's
+ *     target_score for that (row, item) pair.
+ *   - Order, ties, padding and masking are K11's: score descending, then item id ascending; a row with fewer than k unmasked
+ *     items ends with -1 / -inf; a masked item is never returned.  out_item int32 [n, k], out_score fp32 [n, k].
+ *   - The scans of K11 run unchanged over the n KQ query rows; as in K19 mask_row int64 [n KQ] holds row e's entry repeated KQ
+ *     times (the caller repeats it on the device), and mask_row, mask_ptr and mask_idx are all NULL or all non-NULL.  The
+ *     consumer takes the maximum of the KQ adjacent accumulator registers that hold one row's interests (the layout argument
+ *     of K19), so a lane holds 16/KQ evaluation rows, a wave 32/KQ, a workgroup 128/KQ, and threshold, staging count, ballot
+ *     position, workspace region and merge trigger are per EVALUATION row: one item yields at most one candidate per row.
+ *   - out_interest int32 [n, k], may be NULL: the smallest q whose chain equals the returned score, -1 at padding.  A small
+ *     epilogue launch, one thread per (row, slot), recomputes the KQ fmaf chains (bitwise the MFMA's, as K19's target score).
+ *   - KQ in {1, 2, 4} (KQ = 8 would cross the half-wave), D and k as for wr_topk_supported (wr_topk_multi_supported).  With
+ *     KQ = 1 the kernels are those of wr_topk_recommend_rows without query_row and every output has its bits.
+ *   - workspace >= wr_topk_multi_workspace_bytes(n, n_items, D, KQ, k), 16-byte aligned; the bound never decreases as n,
+ *     n_items or k grow, and with KQ = 1 it is wr_topk_workspace_bytes.  n KQ < 2^31, n KQ <= n_query_rows.
+ *   - Argument errors (WR_E_*) are reported before anything is launched.  No host round trip, no float atomics: bitwise
+ *     reproducible. */
+int32_t wr_topk_multi_supported(int32_t D, int32_t KQ, int32_t k);
+int64_t wr_topk_multi_workspace_bytes(int64_t n, int64_t n_items, int32_t D, int32_t KQ, int32_t k);
+int32_t wr_topk_recommend_multi(const float *query_mat, int64_t n_query_rows, const float *item_tab, int64_t n_items,
+                                int32_t D, int32_t KQ, int64_t n, const int64_t *mask_row, int64_t n_mask_rows,
+                                const int64_t *mask_ptr, const int32_t *mask_idx, int32_t k, int32_t *out_item,
+                                float *out_score, int32_t *out_interest /* may be NULL */, void *workspace,
+                                int64_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * K20 SGL's augmented graph views (src/utils/augmentor.py:33-111, csr2tensor of src/models/general/SGL.py:105-146) built on
  *      the device from a resident BASE: the directed edge list (rows, cols) int32 [n_edges] of the symmetric adjacency over
  *      n_nodes nodes, sorted by (row, col) without duplicates; mirror int32 [n_edges], the position of (cols[e], rows[e]);
  *      bchunk_ptr int64 [n_bchunks + 1], the base rows cut into chunks of at most 64 edges that never cross a row, every row

@@ -207,6 +207,10 @@ SIGNATURES = {
                                      c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "wr_rank_eval_multi_supported": (c_i32, [c_i32, c_i32]),
     "wr_rank_eval_multi": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i32, c_i32, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "wr_topk_multi_supported": (c_i32, [c_i32, c_i32, c_i32]),
+    "wr_topk_multi_workspace_bytes": (c_i64, [c_i64, c_i64, c_i32, c_i32, c_i32]),
+    "wr_topk_recommend_multi": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i32, c_i32, c_i64, c_vp, c_i64, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp,
+                                        c_vp, c_i64, c_vp]),
     "wr_sgl_views_workspace_bytes": (c_i64, [c_i64, c_i64]),
     "wr_sgl_view_count": (c_i32, [c_i32, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, ctypes.c_uint64, ctypes.c_uint64,
                                   ctypes.c_uint64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),

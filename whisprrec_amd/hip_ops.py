@@ -1167,13 +1167,14 @@ def topk_supports(D, k):
     return bool(abi.lib().wr_topk_supported(int(D), int(k)))
 
 
-def _topk_blocks(n, n_items, D, k, dev):
+def _topk_blocks(n, n_items, D, k, dev, nbytes=None):
     """(lo, hi, workspace) for n rows in blocks whose workspace stays under TOPK_WORKSPACE_CAP (the bound never decreases in
-    the row count: halve until it fits)"""
+    the row count: halve until it fits).  nbytes(rows): the bound of the entry that is called (wr_topk_workspace_bytes)"""
     L = abi.lib()
 
-    def nbytes(rows):
-        return abi.check_size(L.wr_topk_workspace_bytes(rows, n_items, D, k), "wr_topk_workspace_bytes")
+    if nbytes is None:
+        def nbytes(rows):
+            return abi.check_size(L.wr_topk_workspace_bytes(rows, n_items, D, k), "wr_topk_workspace_bytes")
 
     block = max(n, 1)
     while block > 128 and nbytes(block) > TOPK_WORKSPACE_CAP:
@@ -1314,6 +1315,51 @@ def topk_recommend_rows(query_mat, item_tab, k, mask_row=None, mask_ptr=None, ma
                                            _p(mask_idx), k, _p(items[lo:hi]), _p(scores[lo:hi]), _p(buf), buf.numel(),
                                            _stream()),
                   "wr_topk_recommend_rows")
+    return items.to(torch.int64), scores
+
+
+def topk_multi_supports(D, KQ, k):
+    """(embedding size, queries per row, k) wr_topk_recommend_multi takes (wr_topk_multi_supported): topk_supports' D and k,
+    KQ in {1, 2, 4}"""
+    return bool(abi.lib().wr_topk_multi_supported(int(D), int(KQ), int(k)))
+
+
+def topk_recommend_multi(queries, item_tab, k, mask_row=None, mask_ptr=None, mask_idx=None, with_interest=False):
+    """topk_recommend_rows for a model with KQ query vectors per row (wr_topk_recommend_multi; IF4Rec's interests): queries
+    [n, KQ, D], the score of row e against item j is max_q <queries[e, q], item_tab[j]>, and row e is masked by the list of row
+    mask_row[e] of the CSR (repeated KQ times here, on the device, as in rank_eval_multi).  Order, ties and padding are
+    topk_recommend's; a score is bitwise rank_eval_multi's target_score of that pair.  Returns (items int64 [n, k], scores
+    float32 [n, k]) on the device, and with with_interest=True also interest int64 [n, k]: the smallest q that attains the
+    score, -1 at padding."""
+    _req(queries, torch.float32, "queries", 3)
+    n, KQ, D = (int(v) for v in queries.shape)
+    k = int(k)
+    if not topk_multi_supports(D, KQ, k):
+        raise abi.WhisprRecHipError("topk_recommend_multi does not support D=%d with %d queries per row at k=%d (1 <= k <= %d; D "
+                                    "as for rank_eval; queries per row in {1, 2, 4})" % (D, KQ, k, TOPK_MAX_K))
+    qmat = queries.view(n * KQ, D)
+    _, _, mr = _rows_args("topk_recommend_multi", qmat, item_tab, n, mask_row, mask_ptr, mask_idx, None)
+    if mr is not None:
+        mr = mr.repeat_interleave(KQ).contiguous()
+    L, dev = abi.lib(), queries.device
+    n_items = item_tab.shape[0]
+    n_mask_rows = 0 if mask_ptr is None else mask_ptr.numel() - 1
+    items = torch.empty((n, k), dtype=torch.int32, device=dev)
+    scores = torch.empty((n, k), dtype=torch.float32, device=dev)
+    interest = torch.empty((n, k), dtype=torch.int32, device=dev) if with_interest else None
+
+    def nbytes(rows):
+        return abi.check_size(L.wr_topk_multi_workspace_bytes(rows, n_items, D, KQ, k), "wr_topk_multi_workspace_bytes")
+
+    for lo, hi, buf in _topk_blocks(n, n_items, D, k, dev, nbytes):
+        # a block's queries are the rows lo KQ .. of qmat: the table pointer moves with the block
+        abi.check(L.wr_topk_recommend_multi(_p(qmat[lo * KQ:hi * KQ]), (hi - lo) * KQ, _p(item_tab), n_items, D, KQ, hi - lo,
+                                            _p(mr[lo * KQ:hi * KQ]) if mr is not None else None, n_mask_rows, _p(mask_ptr),
+                                            _p(mask_idx), k, _p(items[lo:hi]), _p(scores[lo:hi]),
+                                            _p(interest[lo:hi]) if with_interest else None, _p(buf), buf.numel(), _stream()),
+                  "wr_topk_recommend_multi")
+    if with_interest:
+        return items.to(torch.int64), scores, interest.to(torch.int64)
     return items.to(torch.int64), scores
 
 

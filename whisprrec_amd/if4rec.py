@@ -28,7 +28,8 @@ Two native paths, both off by default:
 A shape the kernels do not take is logged once and keeps the torch path.
 
 There is no ``eval_queries``: this model has no single query per row.  ``eval_interests`` / ``eval_items`` are the protocol of
-``HipRunner``'s multi-interest ranking (wr_rank_eval_multi, K19).
+``HipRunner``'s multi-interest ranking (wr_rank_eval_multi, K19) and, with ``--interest_topk_native 1``, of its top-K over the
+interests (wr_topk_recommend_multi, K23): ``recommend_rows`` / ``recommend_next`` / ``--save_rec``.
 """
 import logging
 

@@ -7,7 +7,8 @@ Same flow as the reference: pick model / reader / runner classes by name (main.p
 with evaluation on dev every epoch, load the best checkpoint, report test metrics (:30-86).  The corpus pickle cache of
 the reference (:53-63) is not reproduced: the NumPy reader takes a fraction of a second.  Needs a GPU (there is no CPU path).
 With ``--runner_name HipRunner``: ``--save_rec K`` writes the K best items of every dev row (sequential models included, one
-query per row), ``--seq_eval_native 1`` evaluates sequential models on the device.
+query per row), ``--seq_eval_native 1`` evaluates sequential models on the device, ``--interest_topk_native 1`` lets ``--save_rec``
+cover multi-interest models (IF4Rec: the maximum over a row's interests, on the device).
 """
 import argparse
 import logging

@@ -289,6 +289,9 @@ def make_hip_runner(base_runner_cls):
             parser.add_argument("--seq_eval_native", type=int, default=0, choices=[0, 1],
                                 help="1: evaluate sequential models (SASRec) on the device: queries in chunks, ranks from "
                                      "wr_rank_eval_rows, no [n_eval, n_items] matrix; 0: the host loop.")
+            parser.add_argument("--interest_topk_native", type=int, default=0, choices=[0, 1],
+                                help="1: recommend_rows / recommend_next / --save_rec for multi-interest models (IF4Rec) on the "
+                                     "device: the maximum over a row's interests inside wr_topk_recommend_multi; 0: refused.")
             return base_runner_cls.parse_runner_args(parser)
 
         def __init__(self, args):
@@ -296,6 +299,7 @@ def make_hip_runner(base_runner_cls):
             self.device_epoch_prep = int(getattr(args, "device_epoch_prep", 0))
             self.hip_graphs = int(getattr(args, "hip_graphs", 1))
             self.seq_eval_native = bool(int(getattr(args, "seq_eval_native", 0)))
+            self.interest_topk_native = bool(int(getattr(args, "interest_topk_native", 0)))
             self.seed = int(getattr(args, "random_seed", 3407))
             self._epoch_cache = None
             self._hist_cache = {}           # id(dataset) -> (dataset, histories, lengths): train, dev and test alternate
@@ -362,10 +366,16 @@ def make_hip_runner(base_runner_cls):
             """several query vectors per row (``eval_interests`` / ``eval_items``: IF4Rec), scored by their maximum"""
             return hasattr(model, "eval_interests") and hasattr(model, "eval_items")
 
+        @classmethod
+        def _is_multi_interest(cls, model):
+            return cls._has_interest_protocol(model) and not cls._has_query_protocol(model)
+
         def _refuse_multi_interest(self, model, what):
-            if self._has_interest_protocol(model) and not self._has_query_protocol(model):
+            """without --interest_topk_native 1 a multi-interest model has no top-K"""
+            if self._is_multi_interest(model) and not self.interest_topk_native:
                 raise NotImplementedError("%s scores a row by the maximum over several interest vectors (eval_interests): "
-                                          "HipRunner.%s has no top-K over several interests" % (type(model).__name__, what))
+                                          "HipRunner.%s has no top-K over several interests without --interest_topk_native 1"
+                                          % (type(model).__name__, what))
 
         def _seq_eval_ok(self, dataset):
             """--seq_eval_native 1 and a sequential dataset whose model has the query protocol (or the interest protocol, with a
@@ -478,6 +488,10 @@ def make_hip_runner(base_runner_cls):
             from . import hip_ops
             if not hasattr(model, "eval_factors"):
                 self._refuse_multi_interest(model, "recommend")
+                if self._is_multi_interest(model):
+                    raise NotImplementedError("%s scores with several interest vectors per row (eval_interests), not per user: "
+                                              "use HipRunner.recommend_rows(dataset, k) or recommend_next(model, corpus, "
+                                              "histories, k)" % type(model).__name__)
                 if self._has_query_protocol(model):
                     raise NotImplementedError("%s scores with one query per row (eval_queries), not per user: use "
                                               "HipRunner.recommend_rows(dataset, k) or recommend_next(model, corpus, "
@@ -511,20 +525,39 @@ def make_hip_runner(base_runner_cls):
                 return None, None
             raise ValueError("exclude must be 'clicked', 'train' or 'none' (got %r)" % (exclude,))
 
-        def _topk_rows(self, model, corpus, queries, users, k, exclude):
-            """top-K of one query per row, masked by the lists of `users` (None: no mask) -> numpy (items, scores)"""
+        def _topk_rows(self, model, corpus, queries, users, k, exclude, with_interest=False):
+            """top-K of one query per row ([n, D]), or of the maximum over a row's interests ([n, K, D]:
+            wr_topk_recommend_multi), masked by the lists of `users` (None: no mask) -> numpy (items, scores[, interest])"""
             from . import hip_ops
             dev = queries.device
             ptr, idx = self._exclude_mask(corpus, exclude if users is not None else "none", model.user_num, dev)
             mrow = None
             if ptr is not None:
                 mrow = torch.from_numpy(np.ascontiguousarray(np.asarray(users, dtype=np.int64).reshape(-1))).to(dev)
-            items, scores = hip_ops.topk_recommend_rows(queries, model.eval_items().detach().contiguous(), k, mrow, ptr, idx)
-            return items.cpu().numpy(), scores.cpu().numpy()
+            item_tab = model.eval_items().detach().contiguous()
+            if queries.dim() == 3:
+                out = hip_ops.topk_recommend_multi(queries, item_tab, k, mrow, ptr, idx, with_interest=with_interest)
+            else:
+                out = hip_ops.topk_recommend_rows(queries, item_tab, k, mrow, ptr, idx)
+            return tuple(t.cpu().numpy() for t in out)
 
-        def _check_query_model(self, model, k, what):
+        def _check_query_model(self, model, k, what, with_interest=False):
+            """-> does the model score with several interests per row (--interest_topk_native 1)?"""
             from . import hip_ops
+            multi = self._is_multi_interest(model)
+            if with_interest and not multi:
+                raise ValueError("HipRunner.%s: with_interest=True needs a model with several interest vectors per row "
+                                 "(eval_interests); %s has one query per row" % (what, type(model).__name__))
             self._refuse_multi_interest(model, what)
+            if multi:
+                if not hasattr(model, "history_max"):
+                    raise NotImplementedError("%s has no history_max: HipRunner.%s needs a sequential model"
+                                              % (type(model).__name__, what))
+                D, K = model.eval_items().shape[1], int(model.n_interests)
+                if not hip_ops.topk_multi_supports(D, K, k):
+                    raise NotImplementedError("%s: HipRunner.%s does not take %d interests of size %d with k=%d (1, 2 or 4 "
+                                              "interests, k <= %d)" % (type(model).__name__, what, K, D, k, hip_ops.TOPK_MAX_K))
+                return True
             if not self._has_query_protocol(model) or not hasattr(model, "history_max"):
                 raise NotImplementedError("%s has no eval_queries() / eval_items(): HipRunner.%s needs a sequential model "
                                           "with the query protocol" % (type(model).__name__, what))
@@ -532,16 +565,30 @@ def make_hip_runner(base_runner_cls):
             if not hip_ops.topk_supports(D, k):
                 raise NotImplementedError("%s: HipRunner.%s does not support embedding size %d with k=%d"
                                           % (type(model).__name__, what, D, k))
+            return False
 
-        def recommend_rows(self, dataset, k, rows=None, exclude="clicked"):
+        def _row_interests(self, dataset, rows=None):
+            """[n, K, D] interest vectors of the rows of a sequential dataset (`rows`: a subset, in that order)"""
+            model = dataset.model
+            dev = next(model.parameters()).device
+            hist, lens = self._history_columns(dataset, dev)
+            if rows is not None:
+                sel = torch.from_numpy(np.ascontiguousarray(rows)).to(dev)
+                hist, lens = hist[sel], lens[sel]
+            return self._interests_of(model, hist, lens)
+
+        def recommend_rows(self, dataset, k, rows=None, exclude="clicked", with_interest=False):
             """The k best items for rows of a sequential dataset (all of them, or the row numbers `rows` in that order): every
             row scores with the query of its own history (``eval_queries``) and is masked by its user's lists
             (wr_topk_recommend_rows).  `exclude`, order, ties and padding as in ``recommend``.  Returns numpy (items int64
-            [n, k], scores float32 [n, k])."""
+            [n, k], scores float32 [n, k]).  With --interest_topk_native 1 a model with the interest protocol
+            (``eval_interests``: IF4Rec) scores a row by the maximum over its interests (wr_topk_recommend_multi);
+            with_interest=True (such models only) adds interest int64 [n, k], the first interest that attains each score (-1
+            at padding)."""
             model = dataset.model
             if "position" not in dataset.data:
                 raise NotImplementedError("recommend_rows needs a sequential dataset (rows with a position); use recommend")
-            self._check_query_model(model, k, "recommend_rows")
+            multi = self._check_query_model(model, k, "recommend_rows", with_interest)
             users = np.asarray(dataset.data["user_id"], dtype=np.int64)
             if rows is not None:
                 rows = np.asarray(rows, dtype=np.int64).reshape(-1)
@@ -549,13 +596,15 @@ def make_hip_runner(base_runner_cls):
                     raise IndexError("recommend_rows: row number out of range")
                 users = users[rows]
             model.eval()
-            return self._topk_rows(model, dataset.corpus, self._row_queries(dataset, rows), users, k, exclude)
+            queries = self._row_interests(dataset, rows) if multi else self._row_queries(dataset, rows)
+            return self._topk_rows(model, dataset.corpus, queries, users, k, exclude, with_interest)
 
-        def recommend_next(self, model, corpus, histories, k, users=None, exclude="clicked"):
+        def recommend_next(self, model, corpus, histories, k, users=None, exclude="clicked", with_interest=False):
             """The k best next items after each of `histories` (item-id sequences, oldest first; the last history_max items
             count) — histories that need not be in any dataset.  users: the user id behind each history, whose lists
-            `exclude` hides; without users nothing is masked.  Returns numpy (items int64 [n, k], scores float32 [n, k])."""
-            self._check_query_model(model, k, "recommend_next")
+            `exclude` hides; without users nothing is masked.  Returns numpy (items int64 [n, k], scores float32 [n, k]);
+            multi-interest models and with_interest as in ``recommend_rows``."""
+            multi = self._check_query_model(model, k, "recommend_next", with_interest)
             T = int(model.history_max)
             seqs = [np.asarray(h, dtype=np.int64).reshape(-1) for h in histories]
             seqs = [h[-T:] if T > 0 else h for h in seqs]
@@ -569,7 +618,8 @@ def make_hip_runner(base_runner_cls):
                     raise IndexError("recommend_next: user id out of range")
             dev = next(model.parameters()).device
             if not seqs:
-                return np.zeros((0, k), np.int64), np.zeros((0, k), np.float32)
+                empty = (np.zeros((0, k), np.int64), np.zeros((0, k), np.float32))
+                return empty + (np.zeros((0, k), np.int64),) if with_interest else empty
             lens = np.asarray([h.size for h in seqs], dtype=np.int64)
             hist = np.zeros((len(seqs), int(lens.max())), np.int64)
             for r, h in enumerate(seqs):
@@ -577,8 +627,9 @@ def make_hip_runner(base_runner_cls):
             if hist.min() < 0 or hist.max() >= model.item_num:
                 raise IndexError("recommend_next: item id out of range")
             model.eval()
-            queries = self._queries_of(model, torch.from_numpy(hist).to(dev), torch.from_numpy(lens).to(dev))
-            return self._topk_rows(model, corpus, queries, users, k, exclude)
+            hist, lens = torch.from_numpy(hist).to(dev), torch.from_numpy(lens).to(dev)
+            queries = self._interests_of(model, hist, lens) if multi else self._queries_of(model, hist, lens)
+            return self._topk_rows(model, corpus, queries, users, k, exclude, with_interest)
 
         def save_rec_results(self, dataset, k, path, sep="\t"):
             """The reference's save_rec_results (src/main.py:83-102, commented out there): one line per row of `dataset`, in
@@ -587,8 +638,8 @@ def make_hip_runner(base_runner_cls):
             users = np.asarray(dataset.data["user_id"], dtype=np.int64)
             exclude = "clicked" if model.test_all else "none"
             self._refuse_multi_interest(model, "save_rec_results (--save_rec)")
-            if "position" in dataset.data and self._has_query_protocol(model):      # one query per row, not per user
-                items, _ = self.recommend_rows(dataset, k, exclude=exclude)
+            if "position" in dataset.data and (self._has_query_protocol(model) or self._is_multi_interest(model)):
+                items, _ = self.recommend_rows(dataset, k, exclude=exclude)       # queries per row, not per user
             else:
                 items, _ = self.recommend(model, dataset.corpus, users, k, exclude=exclude)
             write_rec_csv(path, users, items, sep)
