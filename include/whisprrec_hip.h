@@ -1137,6 +1137,45 @@ int32_t wr_sgd_rows_sparse(float *tab, int32_t *last_step, int64_t n_rows, int32
                            const int64_t *perm, int64_t n, const float *src, int64_t padding_idx, int64_t step, float lr,
                            float l2, int32_t *err_word, void *stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * K24  K22 for a PAIR (online table `tab`, target table `target`) — BUIR's tables (src/models/general/BUIR.py:69-72): after every
+ *      optimizer step the target follows by target = target*mom + tab*one_minus_mom (the arithmetic of wr_ema_update, K17).
+ *      One last_step per row: last_step[r] = s means row r has had exactly s optimizer steps AND s target updates, in the dense
+ *      order "step 1, update 1, step 2, update 2, ...".  The replay of one missed step is the zero-gradient optimizer step, then
+ *      the target update with the row's new value; under SGD with l2 == 0 the online row stays and the target still moves.
+ *   - Gather: out_tab[k,:] / out_target[k,:] = row idx[k] of both tables as of step `upto`; nothing else is written.
+ *   - Sparse step: sorted_rows / perm / src as for K22 (wr_rows_sparse_keys + a stable sort); no padding row.  Per run of equal
+ *     rows, one wave: the run's sum (ascending position, from +0), replay through step - 1, the step with the sum, the target
+ *     update of that step, then tab, (exp_avg, exp_avg_sq,) target and last_step[row] = step are written.
+ *   - Catch-up: rows [0, n_rows) of the arrays handed in (pointers offset to a window's first row) up to the given step.
+ *   - After a catch-up of the whole table, tab / exp_avg / exp_avg_sq / target hold the bits of "zero table, wr_scatter_add_rows,
+ *     wr_adam_dense / wr_sgd_dense, wr_ema_update" repeated step by step.  One writer per row, no float atomics, no [n_rows, D]
+ *     temporary, no workspace, no allocation, no host round trip.
+ *   - tab, target, exp_avg, exp_avg_sq: 16-byte aligned, 0 < n_rows < 2^31, D a multiple of 4 in [4, 1024] (as K22; the tests
+ *     cover 20, 64 and 128); idx int64, 0 <= n < 2^31; upto / step < n_consts (Adam); mom, one_minus_mom in [0, 1].  Anything else
+ *     is refused (WR_E_*) before any launch.  err_word (int32 on the device, may be NULL; the caller clears and reads it): bit 1
+ *     a row id outside [0, n_rows) — never dereferenced: the gather writes two zero rows, the step skips it —, bit 2 a perm
+ *     entry outside [0, n) (contributes nothing). */
+int32_t wr_gather_rows_ema(const float *tab, const float *target, const float *exp_avg, const float *exp_avg_sq,
+                           const int32_t *last_step, int64_t n_rows, int32_t D, const int64_t *idx, int64_t n, int64_t upto,
+                           const float *consts, int64_t n_consts, float l2, float beta1, float beta2, float eps, float mom,
+                           float one_minus_mom, float *out_tab, float *out_target, int32_t *err_word, void *stream);
+int32_t wr_gather_rows_ema_sgd(const float *tab, const float *target, const int32_t *last_step, int64_t n_rows, int32_t D,
+                               const int64_t *idx, int64_t n, int64_t upto, float lr, float l2, float mom, float one_minus_mom,
+                               float *out_tab, float *out_target, int32_t *err_word, void *stream);
+int32_t wr_adam_rows_sparse_ema(float *tab, float *target, float *exp_avg, float *exp_avg_sq, int32_t *last_step, int64_t n_rows,
+                                int32_t D, const int32_t *sorted_rows, const int64_t *perm, int64_t n, const float *src,
+                                int64_t adam_step, const float *consts, int64_t n_consts, float l2, float beta1, float beta2,
+                                float eps, float mom, float one_minus_mom, int32_t *err_word, void *stream);
+int32_t wr_sgd_rows_sparse_ema(float *tab, float *target, int32_t *last_step, int64_t n_rows, int32_t D,
+                               const int32_t *sorted_rows, const int64_t *perm, int64_t n, const float *src, int64_t step, float lr,
+                               float l2, float mom, float one_minus_mom, int32_t *err_word, void *stream);
+int32_t wr_adam_catchup_ema(float *tab, float *target, float *exp_avg, float *exp_avg_sq, int32_t *last_step, int64_t n_rows,
+                            int32_t D, int64_t adam_step, const float *consts, int64_t n_consts, float l2, float beta1,
+                            float beta2, float eps, float mom, float one_minus_mom, void *stream);
+int32_t wr_sgd_catchup_ema(float *tab, float *target, int32_t *last_step, int64_t n_rows, int32_t D, int64_t step, float lr,
+                           float l2, float mom, float one_minus_mom, void *stream);
+
 /* LightGCN.predict's per-batch tail in two launches (src/models/general/LightGCN.py:156-175, src/utils/loss.py:37-39,94-98):
  *   loss[0] = mean_b( -log(1e-10 + sigmoid(<Ua[u_b], Ia[p_b]> - <Ua[u_b], Ia[n_b]>)) )
  *             + reg_weight * (||U0[u]||_F + ||I0[p]||_F + ||I0[n]||_F) / B

@@ -229,6 +229,17 @@ SIGNATURES = {
     "wr_adam_rows_sparse": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64,
                                     c_f32, c_f32, c_f32, c_f32, c_vp, c_vp]),
     "wr_sgd_rows_sparse": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_f32, c_f32, c_vp, c_vp]),
+    "wr_gather_rows_ema": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_vp, c_i64, c_i64, c_vp, c_i64, c_f32, c_f32, c_f32,
+                                   c_f32, c_f32, c_f32, c_vp, c_vp, c_vp, c_vp]),
+    "wr_gather_rows_ema_sgd": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i32, c_vp, c_i64, c_i64, c_f32, c_f32, c_f32, c_f32, c_vp, c_vp,
+                                       c_vp, c_vp]),
+    "wr_adam_rows_sparse_ema": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64,
+                                        c_f32, c_f32, c_f32, c_f32, c_f32, c_f32, c_vp, c_vp]),
+    "wr_sgd_rows_sparse_ema": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i32, c_vp, c_vp, c_i64, c_vp, c_i64, c_f32, c_f32, c_f32, c_f32,
+                                       c_vp, c_vp]),
+    "wr_adam_catchup_ema": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i64, c_vp, c_i64, c_f32, c_f32, c_f32, c_f32,
+                                    c_f32, c_f32, c_vp]),
+    "wr_sgd_catchup_ema": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i32, c_i64, c_f32, c_f32, c_f32, c_f32, c_vp]),
     "wr_lightgcn_loss_workspace_bytes": (c_i64, [c_i64]),
     "wr_lightgcn_loss": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_vp, c_vp, c_vp, c_i64, c_f32, c_vp, c_vp, c_vp,
                                  c_i64, c_vp]),

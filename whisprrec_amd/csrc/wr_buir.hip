@@ -254,7 +254,7 @@ __global__ __launch_bounds__(kBlock) void buir_fold_kernel(const float *__restri
     }
 }
 
-// K17: t = t m + o (1 - m), three roundings (-ffp-contract=off keeps the products and the sum apart)
+// K17: t = t m + o (1 - m), three roundings (ema_elem of wr_common.h, shared with the row replays of wr_rowopt.hip)
 __global__ __launch_bounds__(kBlock) void ema_kernel(float *__restrict__ t, const float *__restrict__ o, int64_t n, float m,
                                                      float one_minus_m) {
     const int64_t n4 = n >> 2;
@@ -262,15 +262,15 @@ __global__ __launch_bounds__(kBlock) void ema_kernel(float *__restrict__ t, cons
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n4; i += stride) {
         float4 a = reinterpret_cast<float4 *>(t)[i];
         const float4 b = reinterpret_cast<const float4 *>(o)[i];
-        a.x = a.x * m + b.x * one_minus_m;
-        a.y = a.y * m + b.y * one_minus_m;
-        a.z = a.z * m + b.z * one_minus_m;
-        a.w = a.w * m + b.w * one_minus_m;
+        a.x = ema_elem(a.x, b.x, m, one_minus_m);
+        a.y = ema_elem(a.y, b.y, m, one_minus_m);
+        a.z = ema_elem(a.z, b.z, m, one_minus_m);
+        a.w = ema_elem(a.w, b.w, m, one_minus_m);
         reinterpret_cast<float4 *>(t)[i] = a;
     }
     if (blockIdx.x == 0) {
         const int64_t i = (n4 << 2) + threadIdx.x;                        // fewer than 4 elements past the last whole float4
-        if (i < n) t[i] = t[i] * m + o[i] * one_minus_m;
+        if (i < n) t[i] = ema_elem(t[i], o[i], m, one_minus_m);
     }
 }
 

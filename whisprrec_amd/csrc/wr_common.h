@@ -426,4 +426,11 @@ static inline void adam_step_consts(int64_t t, float lr, float beta1, float beta
 // torch.optim.SGD with weight_decay and a zero gradient: g' = 0 + l2*w ; w -= lr*g'
 __device__ __forceinline__ float sgd_decay_elem(float w, float lr, float l2) { return w - lr * (l2 * w); }
 
+// One element of BUIR's momentum update (reference src/models/general/BUIR.py:71): t*m + o*(1 - m) as torch evaluates it — two
+// rounded products and one rounded sum.  The rounding intrinsics keep the three apart whatever the contraction setting, so the
+// dense pass (wr_buir.hip, K17) and the row replays (wr_rowopt.hip, K24) agree bit for bit.
+__device__ __forceinline__ float ema_elem(float t, float o, float m, float one_minus_m) {
+    return __fadd_rn(__fmul_rn(t, m), __fmul_rn(o, one_minus_m));
+}
+
 }  // namespace wr

@@ -2688,6 +2688,144 @@ class RowLazyTable:
         return self.t - int(self.last.min()) if self.stateful else 0
 
 
+class RowLazyEmaTable:
+    """RowLazyTable for a pair (online ``weight``, ``target``) whose target follows the online table by
+    ``target = target*momentum + weight*(1 - momentum)`` after every optimizer step — BUIR's tables (include/whisprrec_hip.h, K24).
+    One step number per row counts optimizer steps and target updates together; ``gather`` returns both rows as of the current
+    step, ``step`` moves the rows of the step only (optimizer step, then their target update), ``flush`` brings all rows up to
+    date.  After a flush, weight, moments and target hold the bits of "zero table, scatter_add_rows, adam_dense / sgd_dense,
+    ema_update_" repeated step by step.  Always stateful: the target of an untouched row moves even under SGD without decay."""
+
+    MAX_LAG, LAG_MIN_GAP = LazyOptimizerState.MAX_LAG, LazyOptimizerState.LAG_MIN_GAP
+    stateful = True
+
+    def __init__(self, weight, target, name, lr, l2, momentum, betas=(0.9, 0.999), eps=1e-8, max_lag=None):
+        """momentum as ema_update_ takes it (rounded to fp32, 1 - momentum formed in double); max_lag as for RowLazyTable"""
+        if name not in ("SGD", "Adam"):
+            raise ValueError(name)
+        _req(weight, torch.float32, "weight", 2)
+        _req(target, torch.float32, "target", 2)
+        if target.shape != weight.shape:
+            raise ValueError("target and weight must have one shape (got %s and %s)" % (tuple(target.shape), tuple(weight.shape)))
+        self.w, self.tgt, self.name, self.lr, self.l2 = weight, target, name, float(lr), float(l2)
+        self.mom, self.one_minus_mom = float(momentum), float(1. - float(momentum))
+        self.betas, self.eps = (float(betas[0]), float(betas[1])), float(eps)
+        self.max_lag = max_lag if max_lag is None else int(max_lag)
+        self.t = 0                               # optimizer steps (and target updates) taken
+        self.flushed_at = 0
+        self._sweep = 0                          # first row of the next window
+        dev = weight.device
+        self.err = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.last = torch.zeros(weight.shape[0], dtype=torch.int32, device=dev)
+        self.m = self.v = self.consts = None
+        if name == "Adam":
+            self.m, self.v = torch.zeros_like(weight), torch.zeros_like(weight)
+            self._grow_consts(4096)
+
+    # the constants table, the lag rule and the rotating window are RowLazyTable's (they go through self._catchup)
+    _grow_consts = RowLazyTable._grow_consts
+    _lag = RowLazyTable._lag
+    _turn_window = RowLazyTable._turn_window
+    behind = RowLazyTable.behind
+
+    def check(self):
+        """one read of the device error word that unchecked gathers and steps leave their findings in"""
+        _raise_row_errors(self.err, "RowLazyEmaTable")
+
+    def gather(self, idx, check=True):
+        """-> (online rows, target rows) at idx[...] as of step t.  check: ids outside the table raise IndexError here (one device
+        read); else they come back as zero rows and the finding waits in the error word for check() / flush()."""
+        flat = _idx64(idx.reshape(-1), "idx")
+        n, (n_rows, D) = flat.numel(), self.w.shape
+        out_w = torch.empty((n, D), dtype=torch.float32, device=self.w.device)
+        out_t = torch.empty((n, D), dtype=torch.float32, device=self.w.device)
+        L = abi.lib()
+        if self.name == "Adam":
+            abi.check(L.wr_gather_rows_ema(_p(self.w), _p(self.tgt), _p(self.m), _p(self.v), _p(self.last), n_rows, D, _p(flat), n,
+                                           self.t, _p(self.consts), self.n_consts, self.l2, self.betas[0], self.betas[1], self.eps,
+                                           self.mom, self.one_minus_mom, _p(out_w), _p(out_t), _p(self.err), _stream()),
+                      "wr_gather_rows_ema")
+        else:
+            abi.check(L.wr_gather_rows_ema_sgd(_p(self.w), _p(self.tgt), _p(self.last), n_rows, D, _p(flat), n, self.t, self.lr,
+                                               self.l2, self.mom, self.one_minus_mom, _p(out_w), _p(out_t), _p(self.err),
+                                               _stream()), "wr_gather_rows_ema_sgd")
+        if check:
+            self.check()
+        shape = tuple(idx.shape) + (D,)
+        return out_w.reshape(shape), out_t.reshape(shape)
+
+    def _catchup(self, lo, count, upto):
+        """rows [lo, lo + count) up to step `upto` (zero gradients, every step followed by its target update)"""
+        L, D = abi.lib(), self.w.shape[1]
+        if self.name == "Adam":
+            abi.check(L.wr_adam_catchup_ema(_p(self.w[lo:]), _p(self.tgt[lo:]), _p(self.m[lo:]), _p(self.v[lo:]), _p(self.last[lo:]),
+                                            count, D, upto, _p(self.consts), self.n_consts, self.l2, self.betas[0], self.betas[1],
+                                            self.eps, self.mom, self.one_minus_mom, _stream()), "wr_adam_catchup_ema")
+        else:
+            abi.check(L.wr_sgd_catchup_ema(_p(self.w[lo:]), _p(self.tgt[lo:]), _p(self.last[lo:]), count, D, upto, self.lr, self.l2,
+                                           self.mom, self.one_minus_mom, _stream()), "wr_sgd_catchup_ema")
+
+    def _order(self, idx_list, grad_list, check):
+        """the step's positions in (row, position) order -> (n, sorted rows, perm, gradient rows), lists concatenated"""
+        if len(idx_list) != len(grad_list):
+            raise ValueError("RowLazyEmaTable.step: as many index tensors as gradient tensors")
+        n_rows, D = self.w.shape
+        idx = [_idx64(i.reshape(-1), "idx") for i in idx_list]
+        grads = [g.reshape(-1, D) for g in grad_list]
+        for i, g in zip(idx, grads):
+            if g.shape[0] != i.numel():
+                raise ValueError("RowLazyEmaTable.step: %d gradient rows for %d indices" % (g.shape[0], i.numel()))
+        n = sum(i.numel() for i in idx)
+        if not n:
+            return 0, None, None, None
+        cat = torch.cat(idx) if len(idx) > 1 else idx[0]
+        rows, perm = rows_sparse_order(cat, n_rows, err_word=self.err)
+        if check:
+            self.check()
+        return n, rows, perm, _req((torch.cat(grads) if len(grads) > 1 else grads[0]).contiguous(), torch.float32, "grad", 2)
+
+    def _window(self, n, t):
+        """before step t with n positions: the constants of step t, and the rotating window up to step t - 1"""
+        if self.name == "Adam" and t >= self.n_consts:
+            self._grow_consts(2 * self.n_consts)
+        lag = self._lag(n)
+        if lag > 0 and t > 1:
+            self._turn_window(lag, t - 1)
+
+    def _apply(self, n, rows, perm, src, t):
+        """step t and its target update on the rows of the step"""
+        if not n:
+            return
+        L, (n_rows, D) = abi.lib(), self.w.shape
+        if self.name == "Adam":
+            abi.check(L.wr_adam_rows_sparse_ema(_p(self.w), _p(self.tgt), _p(self.m), _p(self.v), _p(self.last), n_rows, D, _p(rows),
+                                                _p(perm), n, _p(src), t, _p(self.consts), self.n_consts, self.l2, self.betas[0],
+                                                self.betas[1], self.eps, self.mom, self.one_minus_mom, _p(self.err), _stream()),
+                      "wr_adam_rows_sparse_ema")
+        else:
+            abi.check(L.wr_sgd_rows_sparse_ema(_p(self.w), _p(self.tgt), _p(self.last), n_rows, D, _p(rows), _p(perm), n, _p(src), t,
+                                               self.lr, self.l2, self.mom, self.one_minus_mom, _p(self.err), _stream()),
+                      "wr_sgd_rows_sparse_ema")
+
+    def step(self, idx_list, grad_list, check=True):
+        """optimizer step t + 1 and its target update, with the gradient rows grad_list[i][k, :] of the online rows idx_list[i][k]
+        (lists concatenated in list order).  A step without positions still counts.  check: an id outside the table raises
+        IndexError before anything is written."""
+        n, rows, perm, src = self._order(idx_list, grad_list, check)
+        t = self.t + 1
+        self._window(n, t)
+        self._apply(n, rows, perm, src, t)
+        self.t = t
+
+    def flush(self):
+        """every row up to step t: weight, moments and target are then what the dense optimizer and ema_update_ hold.  A no-op
+        when nothing happened since the last flush.  Also where the findings of unchecked calls are raised."""
+        if self.flushed_at != self.t:
+            self._catchup(0, self.w.shape[0], self.t)
+            self.flushed_at = self.t
+            self.check()
+
+
 class ScatterPlan:
     """Row plan of several scatter-adds whose indices are known ahead (wr_scatter.hip): idx [n_segments, seg_stride] int64
     (segment s uses its first seg_len[s] positions; seg_len int32 on the device, or None = all).  ``apply(table, s, n, src,
