@@ -1208,6 +1208,36 @@ int32_t wr_lightgcn_step(const float *user_tab, const float *item_tab, int64_t n
                          int64_t B, float reg_weight, int32_t trusted_indices, float *loss, float *grad, int32_t *err_flag,
                          void *workspace, int64_t workspace_bytes, void *stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * K25 — time-interval attention (reference src/utils/layers.py:105-146 after the projections), forward and backward, without
+ * the gathered [B, T, T, D] arrays.  q, k, v fp32 [B, T, D] (position terms already added to k and v), times int64 [B, T],
+ * min_interval int64 [B], time_k / time_v fp32 [time_max + 1, D]; head h owns columns h d_k .. (h + 1) d_k - 1; for j <= i:
+ *   r_ij = min(|t_i - t_j| / m_b, time_max)   (64-bit integer division)      s_ij = <q_i, k_j + time_k[r_ij]> / sqrt(d_k)
+ *   p_i. = softmax_j s_i.                                                      out_i = sum_j p_ij (v_j + time_v[r_ij])
+ *   - Supported (wr_ti_attention_supported): D in {32, 64}, n_heads in {1, 2, 4} with D / n_heads >= 8, 1 <= T <= 64,
+ *     1 <= time_max <= 2048 (the intervals are 12-bit fields of the backward's sort keys), 1 <= B <= 2^24.  Anything else, a
+ *     NULL or misaligned (16 B) pointer or a short workspace is refused (WR_E_*) with the numbers before any launch.
+ *   - The softmax subtracts each row's own maximum, not the reference's maximum over the whole call: equal wherever the
+ *     reference is finite; where a row's shifted exponentials all underflow the reference gives NaN, this the plain softmax.
+ *   - wr_ti_attention_fwd: one launch; nothing with T^2 elements per sequence is written to memory.
+ *   - wr_ti_attention_bwd: g_out [B, T, D] -> gq, gk, gv [B, T, D], g_time_k, g_time_v [time_max + 1, D], all fully written.
+ *     The forward is recomputed.  Two launches: every workgroup orders the pairs of a sequence by (r, i, j) in LDS, sums each
+ *     run of equal r in that order and adds it to its own slab [2][time_max + 1][D] of the workspace (sequences w, w + G, ...,
+ *     G = min(B, 256)); the second launch folds the slabs in workgroup order.  No float atomics: same inputs, same bits.
+ *   - min_interval[b] < 1 is clamped to 1 and ORs 1 into err_word (int32 on the device, may be NULL; the caller clears and
+ *     reads it).
+ *   - workspace >= wr_ti_attention_workspace_bytes(B, T, D, n_heads, time_max), 16-byte aligned (backward only): 256 slabs,
+ *     independent of B and T.  No host round trip, no allocation. */
+int32_t wr_ti_attention_supported(int32_t D, int32_t n_heads, int32_t T, int32_t time_max);
+int64_t wr_ti_attention_workspace_bytes(int64_t B, int32_t T, int32_t D, int32_t n_heads, int32_t time_max);
+int32_t wr_ti_attention_fwd(const float *q, const float *k, const float *v, const int64_t *times, const int64_t *min_interval,
+                            int64_t B, int32_t T, int32_t D, int32_t n_heads, const float *time_k, const float *time_v,
+                            int32_t time_max, float *out, int32_t *err_word, void *stream);
+int32_t wr_ti_attention_bwd(const float *q, const float *k, const float *v, const int64_t *times, const int64_t *min_interval,
+                            int64_t B, int32_t T, int32_t D, int32_t n_heads, const float *time_k, const float *time_v,
+                            int32_t time_max, const float *g_out, float *gq, float *gk, float *gv, float *g_time_k,
+                            float *g_time_v, int32_t *err_word, void *workspace, int64_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

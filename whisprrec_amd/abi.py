@@ -245,6 +245,11 @@ SIGNATURES = {
                                  c_i64, c_vp]),
     "wr_embloss_grad": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp, c_f32, c_vp, c_vp, c_vp]),
     "wr_embloss_sumsq": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp]),
+    "wr_ti_attention_supported": (c_i32, [c_i32, c_i32, c_i32, c_i32]),
+    "wr_ti_attention_workspace_bytes": (c_i64, [c_i64, c_i32, c_i32, c_i32, c_i32]),
+    "wr_ti_attention_fwd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp]),
+    "wr_ti_attention_bwd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp,
+                                    c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
 }
 
 

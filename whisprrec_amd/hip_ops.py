@@ -1833,6 +1833,96 @@ def interest_pool(item_weight, pos_weight, history, W1, b1, W2, b2, err_word=Non
     return _InterestPool.apply(item_weight, pos_weight, W1, b1, W2, b2, history, err_word)
 
 
+# ----------------------------------------------------------------------------------------------- time-interval attention (K25)
+def ti_attention_supports(D, n_heads, T, time_max):
+    """shapes wr_ti_attention_fwd / _bwd take (wr_ti_attention_supported): D in {32, 64}, n_heads in {1, 2, 4} with D / n_heads
+    >= 8, T <= 64, time_max <= 2048"""
+    return bool(abi.lib().wr_ti_attention_supported(int(D), int(n_heads), int(T), int(time_max)))
+
+
+def ti_attention_workspace_bytes(B, T, D, n_heads, time_max):
+    return abi.check_size(abi.lib().wr_ti_attention_workspace_bytes(int(B), int(T), int(D), int(n_heads), int(time_max)),
+                          "wr_ti_attention_workspace_bytes")
+
+
+def _ti_attention_args(q, k, v, times, min_interval, time_k, time_v, n_heads, time_max, err_word):
+    """the argument checks of ti_attention_fwd / _bwd -> (B, T, D)"""
+    _req(q, torch.float32, "q", 3)
+    _req(k, torch.float32, "k", 3)
+    _req(v, torch.float32, "v", 3)
+    _req(times, torch.int64, "times", 2)
+    _req(min_interval, torch.int64, "min_interval", 1)
+    _req(time_k, torch.float32, "time_k", 2)
+    _req(time_v, torch.float32, "time_v", 2)
+    B, T, D = (int(x) for x in q.shape)
+    if k.shape != q.shape or v.shape != q.shape or tuple(times.shape) != (B, T) or min_interval.numel() != B:
+        raise ValueError("q, k, v must share one shape [B, T, D], times be [B, T] and min_interval [B] (got %s, %s, %s, %s, %s)"
+                         % (tuple(q.shape), tuple(k.shape), tuple(v.shape), tuple(times.shape), tuple(min_interval.shape)))
+    rows = int(time_max) + 1
+    if tuple(time_k.shape) != (rows, D) or tuple(time_v.shape) != (rows, D):
+        raise ValueError("time_k and time_v must be [time_max + 1, D] = %s (got %s and %s)"
+                         % ((rows, D), tuple(time_k.shape), tuple(time_v.shape)))
+    if B < 1 or D % int(n_heads) or not ti_attention_supports(D, n_heads, T, time_max):
+        raise abi.WhisprRecHipError("ti_attention does not support B=%d T=%d D=%d n_heads=%d time_max=%d (D in {32, 64}, n_heads in "
+                                    "{1, 2, 4} with D / n_heads >= 8, 1 <= T <= 64, 1 <= time_max <= 2048, B >= 1)"
+                                    % (B, T, D, int(n_heads), int(time_max)))
+    if err_word is not None:
+        _req(err_word, torch.int32, "err_word")
+    return B, T, D
+
+
+def ti_attention_fwd(q, k, v, times, min_interval, time_k, time_v, n_heads, time_max, err_word=None):
+    """Time-interval attention [B, T, D] (layers.py:105-146 after the projections) in one launch of wr_ti_attention_fwd: the
+    intervals min(|t_i - t_j| // m_b, time_max) are formed in the kernel and the table rows looked up while the scores are; no
+    [B, T, T, D] gather.  min_interval < 1 is clamped to 1 and ORs 1 into `err_word` (an int32 (1,) device tensor the caller clears
+    and reads, or None)."""
+    B, T, D = _ti_attention_args(q, k, v, times, min_interval, time_k, time_v, n_heads, time_max, err_word)
+    out = torch.empty_like(q)
+    abi.check(abi.lib().wr_ti_attention_fwd(_p(q), _p(k), _p(v), _p(times), _p(min_interval), B, T, D, int(n_heads), _p(time_k),
+                                            _p(time_v), int(time_max), _p(out), _p(err_word), _stream()), "wr_ti_attention_fwd")
+    return out
+
+
+def ti_attention_bwd(q, k, v, times, min_interval, time_k, time_v, n_heads, time_max, g_out, err_word=None):
+    """The gradients of ti_attention_fwd for g_out [B, T, D] (wr_ti_attention_bwd, two launches; the forward is recomputed):
+    (gq, gk, gv, g_time_k, g_time_v).  No float atomics: same inputs, same bits."""
+    B, T, D = _ti_attention_args(q, k, v, times, min_interval, time_k, time_v, n_heads, time_max, err_word)
+    _req(g_out, torch.float32, "g_out", 3)
+    if g_out.shape != q.shape:
+        raise ValueError("g_out must be [B, T, D] = %s (got %s)" % (tuple(q.shape), tuple(g_out.shape)))
+    gq, gk, gv = torch.empty_like(q), torch.empty_like(q), torch.empty_like(q)
+    g_tk, g_tv = torch.empty_like(time_k), torch.empty_like(time_v)
+    ws = workspace(q.device, "ti_attention").get(ti_attention_workspace_bytes(B, T, D, n_heads, time_max))
+    abi.check(abi.lib().wr_ti_attention_bwd(_p(q), _p(k), _p(v), _p(times), _p(min_interval), B, T, D, int(n_heads), _p(time_k),
+                                            _p(time_v), int(time_max), _p(g_out), _p(gq), _p(gk), _p(gv), _p(g_tk), _p(g_tv),
+                                            _p(err_word), _p(ws), ws.numel(), _stream()), "wr_ti_attention_bwd")
+    return gq, gk, gv, g_tk, g_tv
+
+
+class _TiAttention(torch.autograd.Function):
+    """wr_ti_attention_fwd / _bwd: saves the inputs, no activation"""
+
+    @staticmethod
+    def forward(ctx, q, k, v, time_k, time_v, times, min_interval, n_heads, time_max, err_word):
+        args = [t.detach().contiguous() for t in (q, k, v, time_k, time_v)]
+        out = ti_attention_fwd(args[0], args[1], args[2], times, min_interval, args[3], args[4], n_heads, time_max, err_word)
+        ctx.n_heads, ctx.time_max = int(n_heads), int(time_max)
+        ctx.save_for_backward(times, min_interval, *args)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        times, min_interval, q, k, v, time_k, time_v = ctx.saved_tensors
+        gq, gk, gv, g_tk, g_tv = ti_attention_bwd(q, k, v, times, min_interval, time_k, time_v, ctx.n_heads, ctx.time_max,
+                                                  grad_out.contiguous())
+        return gq, gk, gv, g_tk, g_tv, None, None, None, None, None
+
+
+def ti_attention(q, k, v, times, min_interval, time_k, time_v, n_heads, time_max, err_word=None):
+    """ti_attention_fwd under autograd: [B, T, D] whose backward hands back the kernel's gradients of q, k, v and both tables."""
+    return _TiAttention.apply(q, k, v, time_k, time_v, times, min_interval, n_heads, time_max, err_word)
+
+
 def sgd_dense(tab, grad, lr, l2=0.0, stamp=None, step_id=0):
     abi.check(abi.lib().wr_sgd_dense(_p(_req(tab, torch.float32, "tab", 2)), tab.shape[0], tab.shape[1],
                                      _p(_req(grad, torch.float32, "grad", 2)), _p(stamp), step_id, lr, l2, _stream()),

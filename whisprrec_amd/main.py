@@ -19,10 +19,10 @@ import sys
 import numpy as np
 import torch
 
-from . import bprmf, buir, contrarec, if4rec, lightgcn, reader, runner, sasrec, sgl
+from . import bprmf, buir, contrarec, if4rec, lightgcn, reader, runner, sasrec, sgl, tisasrec
 
 MODELS = {"BPRMF": bprmf.BPRMF, "LightGCN": lightgcn.LightGCN, "SGL": sgl.SGL, "SASRec": sasrec.SASRec,
-          "ContraRec": contrarec.ContraRec, "BUIR": buir.BUIR, "IF4Rec": if4rec.IF4Rec}
+          "ContraRec": contrarec.ContraRec, "BUIR": buir.BUIR, "IF4Rec": if4rec.IF4Rec, "TiSASRec": tisasrec.TiSASRec}
 READERS = {"BaseReader": reader.BaseReader, "SeqReader": reader.SeqReader}
 RUNNERS = {"BaseRunner": runner.BaseRunner, "HipRunner": runner.HipRunner}
 

@@ -303,6 +303,7 @@ def make_hip_runner(base_runner_cls):
             self.seed = int(getattr(args, "random_seed", 3407))
             self._epoch_cache = None
             self._hist_cache = {}           # id(dataset) -> (dataset, histories, lengths): train, dev and test alternate
+            self._hist_time_cache = {}      # id(dataset) -> (dataset, history times), for models with needs_history_times
             self._seq_eval_warned = False
 
         def _device_epoch(self, dataset, dev, epoch, pipelined=False):
@@ -410,16 +411,31 @@ def make_hip_runner(base_runner_cls):
             model = dataset.model
             dev = next(model.parameters()).device
             hist, lens = self._history_columns(dataset, dev)
+            times = users = None
+            if self._needs_times(model):     # the timestamps beside the items, and the users whose scale divides the gaps
+                times = self._history_time_columns(dataset, dev)
+                users = torch.from_numpy(np.ascontiguousarray(dataset.data["user_id"])).to(torch.int64).to(dev)
             if rows is not None:
                 sel = torch.from_numpy(np.ascontiguousarray(rows)).to(dev)
                 hist, lens = hist[sel], lens[sel]
-            return self._queries_of(model, hist, lens)
+                if times is not None:
+                    times, users = times[sel], users[sel]
+            return self._queries_of(model, hist, lens, times, users)
 
-        def _queries_of(self, model, hist, lens):
+        @staticmethod
+        def _needs_times(model):
+            """a model whose queries also read each history entry's timestamp and the row's user id (TiSASRec)"""
+            return bool(getattr(model, "needs_history_times", False))
+
+        def _queries_of(self, model, hist, lens, times=None, users=None):
             n, step = hist.shape[0], max(int(self.eval_batch_size), 1)
             out = torch.empty((n, model.eval_items().shape[1]), dtype=torch.float32, device=hist.device)
             for lo in range(0, n, step):
-                out[lo:lo + step] = model.eval_queries(hist[lo:lo + step], lens[lo:lo + step])
+                if times is None:
+                    out[lo:lo + step] = model.eval_queries(hist[lo:lo + step], lens[lo:lo + step])
+                else:
+                    out[lo:lo + step] = model.eval_queries(hist[lo:lo + step], lens[lo:lo + step],
+                                                           history_times=times[lo:lo + step], user_id=users[lo:lo + step])
             return out
 
         def _interests_of(self, model, hist, lens):
@@ -599,14 +615,26 @@ def make_hip_runner(base_runner_cls):
             queries = self._row_interests(dataset, rows) if multi else self._row_queries(dataset, rows)
             return self._topk_rows(model, dataset.corpus, queries, users, k, exclude, with_interest)
 
-        def recommend_next(self, model, corpus, histories, k, users=None, exclude="clicked", with_interest=False):
+        def recommend_next(self, model, corpus, histories, k, users=None, exclude="clicked", with_interest=False, times=None):
             """The k best next items after each of `histories` (item-id sequences, oldest first; the last history_max items
             count) — histories that need not be in any dataset.  users: the user id behind each history, whose lists
             `exclude` hides; without users nothing is masked.  Returns numpy (items int64 [n, k], scores float32 [n, k]);
-            multi-interest models and with_interest as in ``recommend_rows``."""
+            multi-interest models and with_interest as in ``recommend_rows``.  times: the timestamp of every history entry
+            (sequences shaped like `histories`), required together with users for a model that declares
+            ``needs_history_times`` (TiSASRec: the gaps are scaled per user) and ignored by every other model."""
             multi = self._check_query_model(model, k, "recommend_next", with_interest)
             T = int(model.history_max)
             seqs = [np.asarray(h, dtype=np.int64).reshape(-1) for h in histories]
+            tseqs = None
+            if self._needs_times(model):
+                if times is None or users is None:
+                    raise ValueError("recommend_next: %s reads the timestamps of the history and scales their gaps per user: "
+                                     "pass times= (one timestamp per history entry) together with users="
+                                     % type(model).__name__)
+                tseqs = [np.asarray(t, dtype=np.int64).reshape(-1) for t in times]
+                if len(tseqs) != len(seqs) or any(t.size != h.size for t, h in zip(tseqs, seqs)):
+                    raise ValueError("recommend_next: times must hold one timestamp per history entry")
+                tseqs = [t[-T:] if T > 0 else t for t in tseqs]
             seqs = [h[-T:] if T > 0 else h for h in seqs]
             if any(h.size == 0 for h in seqs):
                 raise ValueError("recommend_next: an empty history has no query")
@@ -627,8 +655,14 @@ def make_hip_runner(base_runner_cls):
             if hist.min() < 0 or hist.max() >= model.item_num:
                 raise IndexError("recommend_next: item id out of range")
             model.eval()
+            tcol = ucol = None
+            if tseqs is not None:
+                tcol = np.zeros(hist.shape, np.int64)
+                for r, t in enumerate(tseqs):
+                    tcol[r, :t.size] = t
+                tcol, ucol = torch.from_numpy(tcol).to(dev), torch.from_numpy(users).to(dev)
             hist, lens = torch.from_numpy(hist).to(dev), torch.from_numpy(lens).to(dev)
-            queries = self._interests_of(model, hist, lens) if multi else self._queries_of(model, hist, lens)
+            queries = self._interests_of(model, hist, lens) if multi else self._queries_of(model, hist, lens, tcol, ucol)
             return self._topk_rows(model, corpus, queries, users, k, exclude, with_interest)
 
         def save_rec_results(self, dataset, k, path, sep="\t"):
@@ -728,6 +762,24 @@ def make_hip_runner(base_runner_cls):
             cached = self._hist_cache.get(id(dataset))
             if cached is not None and cached[0] is dataset:
                 return cached[1], cached[2]
+            hist, length = self._history_gather(dataset, 0)
+            out = (torch.from_numpy(hist).to(dev), torch.from_numpy(length).to(dev))
+            self._hist_cache[id(dataset)] = (dataset, out[0], out[1])     # holds the dataset: its id cannot be reused
+            return out
+
+        def _history_time_columns(self, dataset, dev):
+            """the times companion of _history_columns: [n, history_max] int64 timestamps of the same history entries,
+            zero-padded and aligned with the item histories (the reference's `history_times`); built once per dataset"""
+            cached = self._hist_time_cache.get(id(dataset))
+            if cached is not None and cached[0] is dataset:
+                return cached[1]
+            out = torch.from_numpy(self._history_gather(dataset, 1)[0]).to(dev)
+            self._hist_time_cache[id(dataset)] = (dataset, out)
+            return out
+
+        @staticmethod
+        def _history_gather(dataset, field):
+            """-> ([n, width] int64 of entry `field` (0 item, 1 time) of user_his for every row's history, its lengths)"""
             T = int(dataset.model.history_max)
             users = np.asarray(dataset.data["user_id"]).astype(np.int64)
             pos = np.asarray(dataset.data["position"]).astype(np.int64)
@@ -736,16 +788,14 @@ def make_hip_runner(base_runner_cls):
             counts = np.asarray([len(his[int(uu)]) for uu in uniq], dtype=np.int64)
             start_of = np.zeros(int(uniq.max()) + 2, np.int64)
             start_of[uniq] = np.concatenate([[0], np.cumsum(counts)[:-1]])
-            flat = np.concatenate([np.fromiter((x[0] for x in his[int(uu)]), dtype=np.int64, count=len(his[int(uu)])) for uu in uniq])
+            flat = np.concatenate([np.fromiter((x[field] for x in his[int(uu)]), dtype=np.int64, count=len(his[int(uu)]))
+                                   for uu in uniq])
             length = np.minimum(pos, T) if T > 0 else pos
             width = int(length.max()) if length.size else 1
             first = start_of[users] + pos - length
             idx = first[:, None] + np.arange(width)[None, :]
             valid = np.arange(width)[None, :] < length[:, None]
-            hist = np.where(valid, flat[np.minimum(idx, flat.size - 1)], 0)
-            out = (torch.from_numpy(hist).to(dev), torch.from_numpy(length).to(dev))
-            self._hist_cache[id(dataset)] = (dataset, out[0], out[1])     # holds the dataset: its id cannot be reused
-            return out
+            return np.where(valid, flat[np.minimum(idx, flat.size - 1)], 0), length
 
         def fit(self, dataset, epoch=-1):
             model = dataset.model
@@ -787,12 +837,14 @@ def make_hip_runner(base_runner_cls):
                 raise IndexError("index out of range in the training frame")
             model._trusted_indices = True
             losses = []
-            hist = None
+            hist = htime = None
             extras = None    # a model's per-batch additions from the dataset rows of the batch (ContraRec's views, --aug_native 1)
             if sequential:   # the per-row histories travel with the shuffle: same batches as the per-sample collate builds
                 hist_all, len_all = self._history_columns(dataset, dev)
                 order = self._last_order.to(dev)
                 hist, hlen = hist_all[order], len_all[order]
+                if self._needs_times(model):
+                    htime = self._history_time_columns(dataset, dev)[order]
                 extras = getattr(model, "train_batch_extras", None)
                 if extras is not None:
                     model.set_history_table(hist_all, len_all)
@@ -802,6 +854,8 @@ def make_hip_runner(base_runner_cls):
                          "batch_size": min(B, n - lo), "phase": "train"}
                 if hist is not None:
                     batch["history_items"], batch["lengths"] = hist[lo:lo + B], hlen[lo:lo + B]
+                if htime is not None:
+                    batch["history_times"] = htime[lo:lo + B]
                 if extras is not None:
                     extras(batch, order[lo:lo + B], max(epoch, 0))
                 model.optimizer.zero_grad()
@@ -832,8 +886,8 @@ def make_hip_runner(base_runner_cls):
             finally:
                 model._trusted_indices = False
             out = float(torch.stack(losses).mean().cpu())
-            if extras is not None:
-                model.check_train_extras()      # one read of the hook's device error word per epoch
+            if extras is not None or (htime is not None and hasattr(model, "check_train_extras")):
+                model.check_train_extras()      # one read of the model's device error word per epoch
             return out
 
     HipRunner.__qualname__ = "HipRunner"
