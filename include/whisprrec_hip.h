@@ -1238,6 +1238,34 @@ int32_t wr_ti_attention_bwd(const float *q, const float *k, const float *v, cons
                             int32_t time_max, const float *g_out, float *gq, float *gk, float *gv, float *g_time_k,
                             float *g_time_v, int32_t *err_word, void *workspace, int64_t workspace_bytes, void *stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * K26  Softmax cross-entropy of B query rows against the whole item table, loss and both gradients, without the
+ *      [B, n_items] logit matrix (whisprrec_amd/softmax_loss.py, --train_loss softmax --softmax_native 1), fp32.
+ *      Q [B, D] queries, E [n_items, D] item table, target [B] int64; the classes are the items first_class .. n_items - 1
+ *      (first_class = 1: item 0 is padding and no class):
+ *   s_bj  = <Q[b], E[j]>                                  (v_mfma_f32_32x32x2_f32: a k-ordered fmaf chain started at 0)
+ *   loss  = (accumulate ? loss : 0) + weight * sum_b ( log sum_j exp(s_bj) - s_b,target_b )
+ *   gQ[b] = weight * ( sum_j p_bj E[j] - E[target_b] )                p_bj = exp(s_bj) / sum_j' exp(s_bj')
+ *   gE[j] = weight * sum_b ( p_bj - [j == target_b] ) Q[b]            for j >= first_class; rows below are written as zeros
+ *   - The log-sum-exp subtracts the row's true maximum and is exact for any finite scores; the maximum and the shifted
+ *     sum are kept apart, so a row with scores of size 150 loses no more bits than one with scores of size 1.
+ *   - weight = 1 / B gives the mean.  gQ == gE == NULL: loss only, the same loss bits.  gQ [B, D] and gE [n_items, D] are
+ *     fully written; a target named by many rows costs nothing extra (no owner table, no scatter, no memset).
+ *   - Determinism: no float atomics.  Item chunks and query chunks go to partials folded in chunk order, the loss terms in
+ *     a fixed order.  Same inputs, same bits — loss, gQ and gE.
+ *   - Bad targets: a target outside [first_class, n_items) is clamped to the nearest class, never dereferenced, and
+ *     err_word[0] |= 1 (err_word may be NULL; the caller clears it).
+ *   - D in {32, 64, 128} (wr_softmax_ce_supported); any other value, first_class outside [0, n_items), a NULL or misaligned
+ *     (16 B) pointer or a short workspace is refused before a launch.
+ *   - workspace >= wr_softmax_ce_workspace_bytes(n_items, B, D), 16-byte aligned.  The bound grows with max(n_items, B) * D
+ *     and a fixed number of [row, D] chunk partials — never with B * n_items — and never decreases as n_items or B grow.
+ *   - No host round trip, no allocation: capturable into a hipGraph. */
+int32_t wr_softmax_ce_supported(int32_t D);
+int64_t wr_softmax_ce_workspace_bytes(int64_t n_items, int64_t B, int32_t D);
+int32_t wr_softmax_ce_loss_grad(const float *Q, int64_t B, const float *E, int64_t n_items, int32_t D, const int64_t *target,
+                                int64_t first_class, float weight, float *loss, int32_t accumulate, float *gQ, float *gE,
+                                int32_t *err_word, void *workspace, int64_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

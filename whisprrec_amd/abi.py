@@ -250,6 +250,10 @@ SIGNATURES = {
     "wr_ti_attention_fwd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp]),
     "wr_ti_attention_bwd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp,
                                     c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "wr_softmax_ce_supported": (c_i32, [c_i32]),
+    "wr_softmax_ce_workspace_bytes": (c_i64, [c_i64, c_i64, c_i32]),
+    "wr_softmax_ce_loss_grad": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i32, c_vp, c_i64, c_f32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp,
+                                        c_i64, c_vp]),
 }
 
 

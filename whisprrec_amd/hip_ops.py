@@ -1420,6 +1420,98 @@ def infonce_release_workspaces():
     _release_shape_workspaces("infonce")
 
 
+# ----------------------------------------------------------------------------------------------- full-catalogue softmax loss (K26)
+def softmax_ce_supports(D):
+    """embedding sizes wr_softmax_ce_loss_grad takes (wr_softmax_ce_supported)"""
+    return bool(abi.lib().wr_softmax_ce_supported(int(D)))
+
+
+def softmax_ce_workspace_bytes(n, B, D):
+    return abi.check_size(abi.lib().wr_softmax_ce_workspace_bytes(int(n), int(B), int(D)), "wr_softmax_ce_workspace_bytes")
+
+
+def softmax_ce_loss_grad(Q, E, target, *, first_class=1, weight=None, loss=None, grads=True, validate=True, out=None,
+                         err_word=None):
+    """Softmax cross-entropy of the queries Q [B, D] against the whole item table E [n, D] without the [B, n] logit matrix
+    (wr_softmax_ce_loss_grad): loss = weight * sum_b (log sum_{j >= first_class} exp(<Q[b], E[j]>) - <Q[b], E[target_b]>) and its
+    gradients w.r.t. Q and E (rows below first_class of gE are zeros).  `weight=None`: 1 / B, the mean.  `loss`: a (1,) device
+    tensor to ADD the loss to (None = a fresh one).  `grads=False`: loss only, the same bits.  `out=(gQ, gE)`: tensors to write
+    instead of fresh ones.  `validate=False` skips the read-back of the error word (targets already range-checked).
+    `err_word`: the caller's own int32 device word instead — a bad target ORs 1 into it (and is clamped); the caller clears and
+    reads it, nothing is read back here.  Returns (loss, gQ, gE)."""
+    _req(Q, torch.float32, "Q", 2)
+    _req(E, torch.float32, "E", 2)
+    tg = _idx64(target.reshape(-1), "target")
+    B, D = int(Q.shape[0]), int(Q.shape[1])
+    n = int(E.shape[0])
+    if int(E.shape[1]) != D:
+        raise ValueError("Q and E must have one row length (got %s, %s)" % (tuple(Q.shape), tuple(E.shape)))
+    if tg.numel() != B:
+        raise ValueError("target must name one item per row of Q (got %d for %d rows)" % (tg.numel(), B))
+    if not softmax_ce_supports(D):
+        raise abi.WhisprRecHipError("softmax_ce_loss_grad does not support D=%d (D in {32, 64, 128})" % D)
+    if weight is None:
+        weight = 1.0 / B
+    dev = Q.device
+    loss, accumulate = _loss_slot(loss, dev)
+    gQ = gE = None
+    if grads:
+        if out is not None:
+            gQ, gE = out
+            for t, nm, rows in ((gQ, "gQ", B), (gE, "gE", n)):
+                _req(t, torch.float32, nm, 2)
+                if tuple(t.shape) != (rows, D):
+                    raise ValueError("%s must be [%d, %d]" % (nm, rows, D))
+        else:
+            gQ = torch.empty((B, D), dtype=torch.float32, device=dev)
+            gE = torch.empty((n, D), dtype=torch.float32, device=dev)
+    ws, err = _shape_workspace("softmax_ce", dev, (n, B, D), softmax_ce_workspace_bytes, err_word=True)
+    if err_word is not None:
+        err, validate = _req(err_word, torch.int32, "err_word"), False
+    elif validate:
+        err.zero_()
+    else:
+        err = None
+    abi.check(abi.lib().wr_softmax_ce_loss_grad(_p(Q), B, _p(E), n, D, _p(tg), int(first_class), float(weight), _p(loss),
+                                                int(accumulate), _p(gQ), _p(gE), _p(err), _p(ws), ws.numel(), _stream()),
+              "wr_softmax_ce_loss_grad")
+    if validate and int(err.item()) != 0:
+        raise IndexError("softmax_ce_loss_grad: target holds an item outside [%d, %d)" % (int(first_class), n))
+    return loss, gQ, gE
+
+
+def softmax_ce_release_workspaces():
+    """drop the cached workspaces (they are as large as a few tables at big n)"""
+    _release_shape_workspaces("softmax_ce")
+
+
+class _SoftmaxCe(torch.autograd.Function):
+    """loss and both gradients in one call of wr_softmax_ce_loss_grad; the backward scales the stored gradients into NEW tensors
+    (a second backward gives the same gradients, not twice-scaled ones)"""
+
+    @staticmethod
+    def forward(ctx, Q, E, target, first_class, need, err_word):
+        loss, gQ, gE = softmax_ce_loss_grad(Q.detach().contiguous(), E.detach().contiguous(), target, first_class=first_class,
+                                            grads=need, err_word=err_word)
+        if need:
+            ctx.save_for_backward(gQ, gE)
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        gQ, gE = ctx.saved_tensors
+        return (gQ * grad_out if ctx.needs_input_grad[0] else None, gE * grad_out if ctx.needs_input_grad[1] else None, None, None,
+                None, None)
+
+
+def softmax_ce_loss(Q, E, target, first_class=1, err_word=None):
+    """softmax_ce_loss_grad (mean over the batch) under autograd: a 0-d loss whose backward hands Q and E the kernel's gradients.
+    Under torch.no_grad(), or when neither input requires a gradient: loss only.  A target outside [first_class, n) raises
+    IndexError, or (`err_word`: an int32 device word the caller clears and reads) ORs 1 into the word with no host round trip."""
+    need = torch.is_grad_enabled() and (Q.requires_grad or E.requires_grad)
+    return _SoftmaxCe.apply(Q, E, target, int(first_class), need, err_word)
+
+
 # ----------------------------------------------------------------------------------------------- SASRec block (K13)
 SASBLOCK_PARAMS = ("masked_attn_head.q_linear.weight", "masked_attn_head.q_linear.bias", "masked_attn_head.k_linear.weight",
                    "masked_attn_head.k_linear.bias", "masked_attn_head.v_linear.weight", "masked_attn_head.v_linear.bias",

@@ -12,6 +12,8 @@ and evaluation alike; its dropout mask is the kernel's own counter-based generat
 through ``hip_ops.RowLazyTable.gather`` (wr_rowopt.hip, K22: the optimizer steps a row has missed are replayed on the way, nothing
 is written), its backward hands (idx, grad_out) to ``RowLazyOptimizer``, which advances the table row by row exactly as the dense
 optimizer would and leaves every other parameter to ``torch.optim``; ``EmbLazyMixin`` flushes before anything else reads the table.
+``--train_loss softmax`` (SASRec, TiSASRec): ``predict`` returns the cross-entropy against the whole catalogue instead of BPRLoss
+(softmax_loss.py; ``--softmax_native 1``: wr_softmax.hip, K26).
 """
 import logging
 
@@ -20,6 +22,7 @@ import torch
 import torch.nn as nn
 
 from . import hip_ops, host
+from .softmax_loss import SoftmaxLossMixin
 
 
 class _GatherRows(torch.autograd.Function):
@@ -238,10 +241,10 @@ def _xavier_normal_all(module):
 
 
 def make_sasrec(sequential_model_cls):
-    class SASRec(EmbLazyMixin, sequential_model_cls):
+    class SASRec(EmbLazyMixin, SoftmaxLossMixin, sequential_model_cls):
         reader = "SeqReader"
         runner = "BaseRunner"
-        extra_log_args = ["emb_size", "num_layers", "num_heads"]
+        extra_log_args = ["emb_size", "num_layers", "num_heads", "train_loss", "softmax_native"]
 
         @staticmethod
         def parse_model_args(parser):
@@ -252,6 +255,7 @@ def make_sasrec(sequential_model_cls):
             parser.add_argument("--block_native", type=int, default=0, choices=[0, 1],
                                 help="1: each transformer block by the fused HIP kernels (forward and backward); 0: torch ops + autograd.")
             EmbLazyMixin.add_emb_lazy_arg(parser)
+            SoftmaxLossMixin.add_softmax_loss_args(parser)
             return sequential_model_cls.parse_model_args(parser)
 
         def __init__(self, args, corpus):
@@ -267,6 +271,7 @@ def make_sasrec(sequential_model_cls):
             self._block_native_ok = {}   # per history length, decided at its first batch: the library says what it takes
             self._block_seed = int(getattr(args, "random_seed", 0)) * 0x9E3779B97F4A7C15
             self._block_calls = 0        # one dropout stream per training step and layer
+            self._install_softmax_loss(args)
             self._install_emb_lazy(args, self.item_embedding)
 
         def _use_block_native(self, T):
@@ -299,6 +304,8 @@ def make_sasrec(sequential_model_cls):
 
         def predict(self, feed_dict):
             user_e = self.forward(feed_dict)
+            if self.train_loss == "softmax":
+                return self.softmax_loss(user_e, feed_dict["pos_item"])      # neg_items is ignored
             pos_e = self.item_embedding(feed_dict["pos_item"])
             neg_e = self.item_embedding(feed_dict["neg_items"].reshape(-1))
             pos = (user_e * pos_e).sum(dim=1)

@@ -33,6 +33,7 @@ import torch.nn as nn
 
 from . import hip_ops, host
 from .sasrec import EmbLazyMixin, HipEmbedding, _xavier_normal_all
+from .softmax_loss import SoftmaxLossMixin
 
 MIN_INTERVAL_CAP = 65535
 
@@ -126,10 +127,10 @@ class _TiBlock(nn.Module):
 
 
 def make_tisasrec(sequential_model_cls):
-    class TiSASRec(EmbLazyMixin, sequential_model_cls):
+    class TiSASRec(EmbLazyMixin, SoftmaxLossMixin, sequential_model_cls):
         reader = "SeqReader"
         runner = "BaseRunner"
-        extra_log_args = ["emb_size", "num_layers", "num_heads", "time_max"]
+        extra_log_args = ["emb_size", "num_layers", "num_heads", "time_max", "train_loss", "softmax_native"]
         needs_history_times = True       # HipRunner's native loops carry history_times and user_id to this model
 
         @staticmethod
@@ -143,6 +144,7 @@ def make_tisasrec(sequential_model_cls):
                                 help="1: the time-interval attention by the fused HIP kernels (forward and backward), no "
                                      "[B, T, T, D] gather; 0: torch ops + autograd.")
             EmbLazyMixin.add_emb_lazy_arg(parser)
+            SoftmaxLossMixin.add_softmax_loss_args(parser)
             return sequential_model_cls.parse_model_args(parser)
 
         def __init__(self, args, corpus):
@@ -161,6 +163,7 @@ def make_tisasrec(sequential_model_cls):
             self.ti_native = bool(int(getattr(args, "ti_native", 0)))
             self._ti_native_ok = {}      # per history length, decided at its first batch: the library says what it takes
             self._ti_err = None          # device error word of the kernels (a scale below 1), read by check_train_extras()
+            self._install_softmax_loss(args)
             self._install_emb_lazy(args, self.item_embedding)
 
         def _use_ti_native(self, T):
@@ -208,6 +211,8 @@ def make_tisasrec(sequential_model_cls):
 
         def predict(self, feed_dict):
             user_e = self.forward(feed_dict)
+            if self.train_loss == "softmax":
+                return self.softmax_loss(user_e, feed_dict["pos_item"])      # neg_items is ignored
             pos_e = self.item_embedding(feed_dict["pos_item"])
             neg_e = self.item_embedding(feed_dict["neg_items"].reshape(-1))
             pos = (user_e * pos_e).sum(dim=1)
