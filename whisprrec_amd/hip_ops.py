@@ -2638,7 +2638,7 @@ def scatter_add_rows(grad, idx, src, padding_idx=-1, alpha=1.0):
     return grad
 
 
-# ----------------------------------------------------------------------------------------------- row-lazy optimizers (K22)
+# ------------------------------------------------------------------------------------------ row-lazy optimizers (K22, K24)
 ROW_ERR_ID, ROW_ERR_PERM = 1, 2          # bits of the kernels' device error word
 
 
@@ -2650,38 +2650,6 @@ def _raise_row_errors(err, what):
         raise IndexError("%s: %s" % (what, " and ".join(
             t for bit, t in ((ROW_ERR_ID, "a row id outside the table"), (ROW_ERR_PERM, "a position outside the step's rows"))
             if word & bit)))
-
-
-def gather_rows_lazy(tab, exp_avg, exp_avg_sq, last, idx, upto, consts, l2=0.0, beta1=0.9, beta2=0.999, eps=1e-8, err_word=None):
-    """out[..., :] = row idx[...] of `tab` as dense Adam holds it after step `upto` (wr_gather_rows_lazy): the steps
-    last[row]+1 .. upto are replayed in registers, nothing but `out` is written.  err_word given: ids outside the table set
-    bit 1 there (their output rows are zeros) and the caller reads it; None: checked here, IndexError."""
-    for t, nm in ((tab, "tab"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
-        _req(t, torch.float32, nm, 2)
-    _req(last, torch.int32, "last", 1)
-    flat = _idx64(idx.reshape(-1), "idx")
-    out = torch.empty((flat.numel(), tab.shape[1]), dtype=torch.float32, device=tab.device)
-    err = err_word if err_word is not None else torch.zeros(1, dtype=torch.int32, device=tab.device)
-    abi.check(abi.lib().wr_gather_rows_lazy(_p(tab), _p(exp_avg), _p(exp_avg_sq), _p(last), tab.shape[0], tab.shape[1], _p(flat),
-                                            flat.numel(), int(upto), _p(consts), consts.numel() // 2, l2, beta1, beta2, eps,
-                                            _p(out), _p(err), _stream()), "wr_gather_rows_lazy")
-    if err_word is None:
-        _raise_row_errors(err, "gather_rows_lazy")
-    return out.reshape(tuple(idx.shape) + (tab.shape[1],))
-
-
-def gather_rows_lazy_sgd(tab, last, idx, upto, lr, l2, err_word=None):
-    """gather_rows_lazy for SGD with weight decay: the missed decays w <- w - lr*l2*w are replayed (wr_gather_rows_lazy_sgd)"""
-    _req(tab, torch.float32, "tab", 2)
-    _req(last, torch.int32, "last", 1)
-    flat = _idx64(idx.reshape(-1), "idx")
-    out = torch.empty((flat.numel(), tab.shape[1]), dtype=torch.float32, device=tab.device)
-    err = err_word if err_word is not None else torch.zeros(1, dtype=torch.int32, device=tab.device)
-    abi.check(abi.lib().wr_gather_rows_lazy_sgd(_p(tab), _p(last), tab.shape[0], tab.shape[1], _p(flat), flat.numel(), int(upto),
-                                                lr, l2, _p(out), _p(err), _stream()), "wr_gather_rows_lazy_sgd")
-    if err_word is None:
-        _raise_row_errors(err, "gather_rows_lazy_sgd")
-    return out.reshape(tuple(idx.shape) + (tab.shape[1],))
 
 
 def rows_sparse_order(idx, n_rows, err_word=None):
@@ -2698,68 +2666,58 @@ def rows_sparse_order(idx, n_rows, err_word=None):
     return torch.sort(keys, stable=True)
 
 
-def adam_rows_sparse(tab, exp_avg, exp_avg_sq, last, sorted_rows, perm, src, adam_step, consts, l2=0.0, beta1=0.9, beta2=0.999,
-                     eps=1e-8, padding_idx=-1, err_word=None):
-    """torch.optim.Adam's step `adam_step` on the rows of sorted_rows only (wr_adam_rows_sparse): per run of equal rows the sum
-    of src[perm[q]] in ascending q, the row's missed zero-gradient steps, the step; last[row] = adam_step.  In place."""
-    for t, nm in ((tab, "tab"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
-        _req(t, torch.float32, nm, 2)
-    _req(last, torch.int32, "last", 1)
-    _req(sorted_rows, torch.int32, "sorted_rows", 1)
-    _req(perm, torch.int64, "perm", 1)
-    n = sorted_rows.numel()
-    src2 = _req(src.reshape(-1, tab.shape[1]), torch.float32, "src", 2)
-    if perm.numel() != n or src2.shape[0] != n:
-        raise ValueError("adam_rows_sparse: sorted_rows, perm and src must hold the same number of positions")
-    abi.check(abi.lib().wr_adam_rows_sparse(_p(tab), _p(exp_avg), _p(exp_avg_sq), _p(last), tab.shape[0], tab.shape[1],
-                                            _p(sorted_rows), _p(perm), n, _p(src2), int(padding_idx), int(adam_step), _p(consts),
-                                            consts.numel() // 2, l2, beta1, beta2, eps, _p(err_word), _stream()),
-              "wr_adam_rows_sparse")
-
-
-def sgd_rows_sparse(tab, last, sorted_rows, perm, src, step, lr, l2=0.0, padding_idx=-1, err_word=None):
-    """torch.optim.SGD's step on the rows of sorted_rows only (wr_sgd_rows_sparse); last: int32 [n_rows], or None when l2 == 0"""
-    _req(tab, torch.float32, "tab", 2)
-    if last is not None:
-        _req(last, torch.int32, "last", 1)
-    elif l2 != 0.0:
-        raise ValueError("sgd_rows_sparse: weight decay needs the rows' last steps")
-    _req(sorted_rows, torch.int32, "sorted_rows", 1)
-    _req(perm, torch.int64, "perm", 1)
-    n = sorted_rows.numel()
-    src2 = _req(src.reshape(-1, tab.shape[1]), torch.float32, "src", 2)
-    if perm.numel() != n or src2.shape[0] != n:
-        raise ValueError("sgd_rows_sparse: sorted_rows, perm and src must hold the same number of positions")
-    abi.check(abi.lib().wr_sgd_rows_sparse(_p(tab), _p(last), tab.shape[0], tab.shape[1], _p(sorted_rows), _p(perm), n, _p(src2),
-                                           int(padding_idx), int(step), lr, l2, _p(err_word), _stream()), "wr_sgd_rows_sparse")
-
-
 class RowLazyTable:
-    """torch.optim.Adam / SGD(weight_decay) on ONE table whose gradient arrives as (index, gradient row) pairs — the item table of
-    the sequential models (include/whisprrec_hip.h, K22).  Every row carries the number of the last optimizer step applied to
-    it; ``gather`` returns rows as of the current step without writing anything, ``step`` moves the rows of the step only,
-    ``flush`` brings all rows up to date — call it before anything else reads ``weight``.  After a flush, weight and moments
-    hold the bits of "zero table, scatter_add_rows, adam_dense / sgd_dense" repeated step by step."""
+    """torch.optim.Adam / SGD(weight_decay) on a table whose gradient arrives as (index, gradient row) pairs (wr_rowopt.hip;
+    include/whisprrec_hip.h, K22 and K24).  Every row carries the number of the last optimizer step applied to it; ``gather``
+    returns rows as of the current step without writing anything, ``step`` moves the rows of the step only, ``flush`` brings
+    all rows up to date — call it before anything else reads ``weight``.  Two faces:
+      ONE table (the item table of the sequential models): after a flush, weight and moments hold the bits of "zero table,
+        scatter_add_rows, adam_dense / sgd_dense" repeated step by step.  Under SGD without decay an untouched row never moves:
+        no state.
+      a PAIR (``target`` given: BUIR's online and target tables): the target follows the online table by ``target =
+        target*momentum + weight*(1 - momentum)`` after every optimizer step; one step number per row counts optimizer steps and
+        target updates together, ``gather`` returns both rows, ``step`` ends with the target update of its rows, and after a
+        flush the target too holds the bits of the dense loop with ``ema_update_``.  Always stateful: the target of an
+        untouched row moves even under SGD without decay."""
 
     MAX_LAG, LAG_MIN_GAP = LazyOptimizerState.MAX_LAG, LazyOptimizerState.LAG_MIN_GAP
+    # the entry of an operation by (Adam, pair)
+    ENTRIES = {"gather": {(True, False): "wr_gather_rows_lazy", (False, False): "wr_gather_rows_lazy_sgd",
+                          (True, True): "wr_gather_rows_ema", (False, True): "wr_gather_rows_ema_sgd"},
+               "step": {(True, False): "wr_adam_rows_sparse", (False, False): "wr_sgd_rows_sparse",
+                        (True, True): "wr_adam_rows_sparse_ema", (False, True): "wr_sgd_rows_sparse_ema"},
+               "catchup": {(True, False): "wr_adam_catchup_all", (False, False): "wr_sgd_catchup_all",
+                           (True, True): "wr_adam_catchup_ema", (False, True): "wr_sgd_catchup_ema"}}
 
-    def __init__(self, weight, name, lr, l2, betas=(0.9, 0.999), eps=1e-8, max_lag=None, padding_idx=-1):
+    def __init__(self, weight, name, lr, l2, betas=(0.9, 0.999), eps=1e-8, max_lag=None, padding_idx=-1, target=None,
+                 momentum=None):
         """max_lag as for LazyOptimizerState: None = MAX_LAG when a row misses more than LAG_MIN_GAP steps between two uses on
         average (rows / positions of the step), 0 = unbounded, n = before every step a rotating window of rows / n rows is
-        brought up to date (wr_adam_catchup_all / wr_sgd_catchup_all on the window), so that no row ever lags more than n."""
+        brought up to date, so that no row ever lags more than n.  momentum (with target) as ema_update_ takes it: rounded to
+        fp32, 1 - momentum formed in double.  A pair has no padding row."""
         if name not in ("SGD", "Adam"):
             raise ValueError(name)
         _req(weight, torch.float32, "weight", 2)
+        self.tgt = self.mom = self.one_minus_mom = None
+        if target is not None:
+            _req(target, torch.float32, "target", 2)
+            if target.shape != weight.shape:
+                raise ValueError("target and weight must have one shape (got %s and %s)" % (tuple(target.shape), tuple(weight.shape)))
+            if momentum is None or int(padding_idx) != -1:
+                raise ValueError("a pair of tables needs a momentum and has no padding row")
+            self.tgt, self.mom, self.one_minus_mom = target, float(momentum), float(1. - float(momentum))
+        elif momentum is not None:
+            raise ValueError("momentum without a target")
         self.w, self.name, self.lr, self.l2 = weight, name, float(lr), float(l2)
         self.betas, self.eps = (float(betas[0]), float(betas[1])), float(eps)
         self.max_lag = max_lag if max_lag is None else int(max_lag)
         self.padding_idx = int(padding_idx)
-        self.t = 0                               # optimizer steps taken
+        self.t = 0                               # optimizer steps (and target updates) taken
         self.flushed_at = 0
         self._sweep = 0                          # first row of the next window
         dev = weight.device
         self.err = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.stateful = name == "Adam" or self.l2 != 0.0      # SGD without decay: untouched rows never move
+        self.stateful = name == "Adam" or self.l2 != 0.0 or target is not None
         self.m = self.v = self.last = self.consts = None
         if self.stateful:
             self.last = torch.zeros(weight.shape[0], dtype=torch.int32, device=dev)
@@ -2773,38 +2731,43 @@ class RowLazyTable:
         self.consts = host.to(self.w.device)
         self.n_consts = n
 
+    def _call(self, op, lo, n_rows, mid, tail=()):
+        """one entry of wr_rowopt.hip / wr_lazy.hip, by this table's optimizer and face: (the tables from row lo on, n_rows, D,
+        *mid, the optimizer's constants, *tail, stream)"""
+        adam, pair = self.name == "Adam", self.tgt is not None
+        entry = self.ENTRIES[op][adam, pair]
+        tabs = [self.w] + ([self.tgt] if pair else []) + ([self.m, self.v] if adam else []) + [self.last]
+        opt = (_p(self.consts), self.n_consts, self.l2, *self.betas, self.eps) if adam else (self.lr, self.l2)
+        if pair:
+            opt += (self.mom, self.one_minus_mom)
+        abi.check(getattr(abi.lib(), entry)(*(_p(t[lo:] if lo else t) for t in tabs), n_rows, self.w.shape[1], *mid, *opt, *tail,
+                                            _stream()), entry)
+
     def check(self):
         """one read of the device error word that unchecked gathers and steps leave their findings in"""
-        _raise_row_errors(self.err, "RowLazyTable")
+        _raise_row_errors(self.err, type(self).__name__)
 
     def gather(self, idx, check=True):
-        """rows idx[...] as of step t.  check: ids outside the table raise IndexError here (one device read); else they come
-        back as zero rows and the finding waits in the error word for check() / flush()."""
+        """rows idx[...] as of step t; a pair: -> (online rows, target rows).  check: ids outside the table raise IndexError here
+        (one device read); else they come back as zero rows and the finding waits in the error word for check() / flush()."""
         if not self.stateful:
             if check:
                 flat = idx.reshape(-1)
                 if flat.numel() and (int(flat.min()) < 0 or int(flat.max()) >= self.w.shape[0]):
                     raise IndexError("RowLazyTable: a row id outside the table")
             return gather_rows(self.w, idx)
-        if self.name == "Adam":
-            out = gather_rows_lazy(self.w, self.m, self.v, self.last, idx, self.t, self.consts, self.l2, *self.betas, self.eps,
-                                   err_word=self.err)
-        else:
-            out = gather_rows_lazy_sgd(self.w, self.last, idx, self.t, self.lr, self.l2, err_word=self.err)
+        flat = _idx64(idx.reshape(-1), "idx")
+        n, (n_rows, D) = flat.numel(), self.w.shape
+        outs = [torch.empty((n, D), dtype=torch.float32, device=self.w.device) for _ in range(1 if self.tgt is None else 2)]
+        self._call("gather", 0, n_rows, (_p(flat), n, self.t), (*map(_p, outs), _p(self.err)))
         if check:
             self.check()
-        return out
+        outs = [o.reshape(tuple(idx.shape) + (D,)) for o in outs]
+        return outs[0] if self.tgt is None else tuple(outs)
 
     def _catchup(self, lo, count, upto):
-        """rows [lo, lo + count) up to step `upto` (zero gradients)"""
-        L, D = abi.lib(), self.w.shape[1]
-        if self.name == "Adam":
-            abi.check(L.wr_adam_catchup_all(_p(self.w[lo:]), _p(self.m[lo:]), _p(self.v[lo:]), _p(self.last[lo:]), count, D, upto,
-                                            _p(self.consts), self.n_consts, self.l2, self.betas[0], self.betas[1], self.eps,
-                                            _stream()), "wr_adam_catchup_all")
-        else:
-            abi.check(L.wr_sgd_catchup_all(_p(self.w[lo:]), _p(self.last[lo:]), count, D, upto, self.lr, self.l2, _stream()),
-                      "wr_sgd_catchup_all")
+        """rows [lo, lo + count) up to step `upto` (zero gradients; a pair: every step followed by its target update)"""
+        self._call("catchup", lo, count, (upto,))
 
     def _lag(self, n_positions):
         if self.max_lag is None:
@@ -2821,142 +2784,17 @@ class RowLazyTable:
             lo, left = (lo + c) % n_rows, left - c
         self._sweep = lo
 
-    def step(self, idx_list, grad_list, check=True):
-        """optimizer step t + 1 with the gradient rows grad_list[i][k, :] of the rows idx_list[i][k]: the lists are concatenated
-        in list order (the order of the forward lookups), brought into (row, position) order, the window is turned and the
-        step's rows are moved.  check: an id outside the table raises IndexError before anything is written."""
-        if len(idx_list) != len(grad_list):
-            raise ValueError("RowLazyTable.step: as many index tensors as gradient tensors")
-        D = self.w.shape[1]
-        idx = [_idx64(i.reshape(-1), "idx") for i in idx_list]
-        grads = [g.reshape(-1, D) for g in grad_list]
-        for i, g in zip(idx, grads):
-            if g.shape[0] != i.numel():
-                raise ValueError("RowLazyTable.step: %d gradient rows for %d indices" % (g.shape[0], i.numel()))
-        n = sum(i.numel() for i in idx)
-        if n:
-            cat = torch.cat(idx) if len(idx) > 1 else idx[0]
-            rows, perm = rows_sparse_order(cat, self.w.shape[0], err_word=self.err)
-            if check:
-                self.check()
-            src = _req((torch.cat(grads) if len(grads) > 1 else grads[0]).contiguous(), torch.float32, "grad", 2)
-        t = self.t + 1
-        if self.stateful:
-            if self.name == "Adam" and t >= self.n_consts:
-                self._grow_consts(2 * self.n_consts)
-            lag = self._lag(n)
-            if lag > 0 and t > 1:
-                self._turn_window(lag, t - 1)
-        if n:
-            if self.name == "Adam":
-                adam_rows_sparse(self.w, self.m, self.v, self.last, rows, perm, src, t, self.consts, self.l2, *self.betas, self.eps,
-                                 padding_idx=self.padding_idx, err_word=self.err)
-            else:
-                sgd_rows_sparse(self.w, self.last, rows, perm, src, t, self.lr, self.l2, padding_idx=self.padding_idx,
-                                err_word=self.err)
-        self.t = t
-
-    def flush(self):
-        """every row up to step t: weight (and the moments) are then what the dense optimizer holds.  A no-op when nothing
-        happened since the last flush.  Also where the findings of unchecked calls are raised."""
-        if self.flushed_at != self.t:
-            if self.stateful:
-                self._catchup(0, self.w.shape[0], self.t)
-            self.flushed_at = self.t
-            self.check()
-
-    def behind(self):
-        """steps the most outdated row lags behind (one device read)"""
-        return self.t - int(self.last.min()) if self.stateful else 0
-
-
-class RowLazyEmaTable:
-    """RowLazyTable for a pair (online ``weight``, ``target``) whose target follows the online table by
-    ``target = target*momentum + weight*(1 - momentum)`` after every optimizer step — BUIR's tables (include/whisprrec_hip.h, K24).
-    One step number per row counts optimizer steps and target updates together; ``gather`` returns both rows as of the current
-    step, ``step`` moves the rows of the step only (optimizer step, then their target update), ``flush`` brings all rows up to
-    date.  After a flush, weight, moments and target hold the bits of "zero table, scatter_add_rows, adam_dense / sgd_dense,
-    ema_update_" repeated step by step.  Always stateful: the target of an untouched row moves even under SGD without decay."""
-
-    MAX_LAG, LAG_MIN_GAP = LazyOptimizerState.MAX_LAG, LazyOptimizerState.LAG_MIN_GAP
-    stateful = True
-
-    def __init__(self, weight, target, name, lr, l2, momentum, betas=(0.9, 0.999), eps=1e-8, max_lag=None):
-        """momentum as ema_update_ takes it (rounded to fp32, 1 - momentum formed in double); max_lag as for RowLazyTable"""
-        if name not in ("SGD", "Adam"):
-            raise ValueError(name)
-        _req(weight, torch.float32, "weight", 2)
-        _req(target, torch.float32, "target", 2)
-        if target.shape != weight.shape:
-            raise ValueError("target and weight must have one shape (got %s and %s)" % (tuple(target.shape), tuple(weight.shape)))
-        self.w, self.tgt, self.name, self.lr, self.l2 = weight, target, name, float(lr), float(l2)
-        self.mom, self.one_minus_mom = float(momentum), float(1. - float(momentum))
-        self.betas, self.eps = (float(betas[0]), float(betas[1])), float(eps)
-        self.max_lag = max_lag if max_lag is None else int(max_lag)
-        self.t = 0                               # optimizer steps (and target updates) taken
-        self.flushed_at = 0
-        self._sweep = 0                          # first row of the next window
-        dev = weight.device
-        self.err = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.last = torch.zeros(weight.shape[0], dtype=torch.int32, device=dev)
-        self.m = self.v = self.consts = None
-        if name == "Adam":
-            self.m, self.v = torch.zeros_like(weight), torch.zeros_like(weight)
-            self._grow_consts(4096)
-
-    # the constants table, the lag rule and the rotating window are RowLazyTable's (they go through self._catchup)
-    _grow_consts = RowLazyTable._grow_consts
-    _lag = RowLazyTable._lag
-    _turn_window = RowLazyTable._turn_window
-    behind = RowLazyTable.behind
-
-    def check(self):
-        """one read of the device error word that unchecked gathers and steps leave their findings in"""
-        _raise_row_errors(self.err, "RowLazyEmaTable")
-
-    def gather(self, idx, check=True):
-        """-> (online rows, target rows) at idx[...] as of step t.  check: ids outside the table raise IndexError here (one device
-        read); else they come back as zero rows and the finding waits in the error word for check() / flush()."""
-        flat = _idx64(idx.reshape(-1), "idx")
-        n, (n_rows, D) = flat.numel(), self.w.shape
-        out_w = torch.empty((n, D), dtype=torch.float32, device=self.w.device)
-        out_t = torch.empty((n, D), dtype=torch.float32, device=self.w.device)
-        L = abi.lib()
-        if self.name == "Adam":
-            abi.check(L.wr_gather_rows_ema(_p(self.w), _p(self.tgt), _p(self.m), _p(self.v), _p(self.last), n_rows, D, _p(flat), n,
-                                           self.t, _p(self.consts), self.n_consts, self.l2, self.betas[0], self.betas[1], self.eps,
-                                           self.mom, self.one_minus_mom, _p(out_w), _p(out_t), _p(self.err), _stream()),
-                      "wr_gather_rows_ema")
-        else:
-            abi.check(L.wr_gather_rows_ema_sgd(_p(self.w), _p(self.tgt), _p(self.last), n_rows, D, _p(flat), n, self.t, self.lr,
-                                               self.l2, self.mom, self.one_minus_mom, _p(out_w), _p(out_t), _p(self.err),
-                                               _stream()), "wr_gather_rows_ema_sgd")
-        if check:
-            self.check()
-        shape = tuple(idx.shape) + (D,)
-        return out_w.reshape(shape), out_t.reshape(shape)
-
-    def _catchup(self, lo, count, upto):
-        """rows [lo, lo + count) up to step `upto` (zero gradients, every step followed by its target update)"""
-        L, D = abi.lib(), self.w.shape[1]
-        if self.name == "Adam":
-            abi.check(L.wr_adam_catchup_ema(_p(self.w[lo:]), _p(self.tgt[lo:]), _p(self.m[lo:]), _p(self.v[lo:]), _p(self.last[lo:]),
-                                            count, D, upto, _p(self.consts), self.n_consts, self.l2, self.betas[0], self.betas[1],
-                                            self.eps, self.mom, self.one_minus_mom, _stream()), "wr_adam_catchup_ema")
-        else:
-            abi.check(L.wr_sgd_catchup_ema(_p(self.w[lo:]), _p(self.tgt[lo:]), _p(self.last[lo:]), count, D, upto, self.lr, self.l2,
-                                           self.mom, self.one_minus_mom, _stream()), "wr_sgd_catchup_ema")
-
     def _order(self, idx_list, grad_list, check):
         """the step's positions in (row, position) order -> (n, sorted rows, perm, gradient rows), lists concatenated"""
+        who = type(self).__name__
         if len(idx_list) != len(grad_list):
-            raise ValueError("RowLazyEmaTable.step: as many index tensors as gradient tensors")
+            raise ValueError("%s.step: as many index tensors as gradient tensors" % who)
         n_rows, D = self.w.shape
         idx = [_idx64(i.reshape(-1), "idx") for i in idx_list]
         grads = [g.reshape(-1, D) for g in grad_list]
         for i, g in zip(idx, grads):
             if g.shape[0] != i.numel():
-                raise ValueError("RowLazyEmaTable.step: %d gradient rows for %d indices" % (g.shape[0], i.numel()))
+                raise ValueError("%s.step: %d gradient rows for %d indices" % (who, g.shape[0], i.numel()))
         n = sum(i.numel() for i in idx)
         if not n:
             return 0, None, None, None
@@ -2968,6 +2806,8 @@ class RowLazyEmaTable:
 
     def _window(self, n, t):
         """before step t with n positions: the constants of step t, and the rotating window up to step t - 1"""
+        if not self.stateful:
+            return
         if self.name == "Adam" and t >= self.n_consts:
             self._grow_consts(2 * self.n_consts)
         lag = self._lag(n)
@@ -2975,24 +2815,16 @@ class RowLazyEmaTable:
             self._turn_window(lag, t - 1)
 
     def _apply(self, n, rows, perm, src, t):
-        """step t and its target update on the rows of the step"""
-        if not n:
-            return
-        L, (n_rows, D) = abi.lib(), self.w.shape
-        if self.name == "Adam":
-            abi.check(L.wr_adam_rows_sparse_ema(_p(self.w), _p(self.tgt), _p(self.m), _p(self.v), _p(self.last), n_rows, D, _p(rows),
-                                                _p(perm), n, _p(src), t, _p(self.consts), self.n_consts, self.l2, self.betas[0],
-                                                self.betas[1], self.eps, self.mom, self.one_minus_mom, _p(self.err), _stream()),
-                      "wr_adam_rows_sparse_ema")
-        else:
-            abi.check(L.wr_sgd_rows_sparse_ema(_p(self.w), _p(self.tgt), _p(self.last), n_rows, D, _p(rows), _p(perm), n, _p(src), t,
-                                               self.lr, self.l2, self.mom, self.one_minus_mom, _p(self.err), _stream()),
-                      "wr_sgd_rows_sparse_ema")
+        """step t (a pair: and its target update) on the rows of the step"""
+        if n:
+            pad = () if self.tgt is not None else (self.padding_idx,)
+            self._call("step", 0, self.w.shape[0], (_p(rows), _p(perm), n, _p(src), *pad, t), (_p(self.err),))
 
     def step(self, idx_list, grad_list, check=True):
-        """optimizer step t + 1 and its target update, with the gradient rows grad_list[i][k, :] of the online rows idx_list[i][k]
-        (lists concatenated in list order).  A step without positions still counts.  check: an id outside the table raises
-        IndexError before anything is written."""
+        """optimizer step t + 1 (a pair: and its target update) with the gradient rows grad_list[i][k, :] of the rows
+        idx_list[i][k]: the lists are concatenated in list order (the order of the forward lookups), brought into (row, position)
+        order, the window is turned and the step's rows are moved.  A step without positions still counts.  check: an id outside
+        the table raises IndexError before anything is written."""
         n, rows, perm, src = self._order(idx_list, grad_list, check)
         t = self.t + 1
         self._window(n, t)
@@ -3000,12 +2832,24 @@ class RowLazyEmaTable:
         self.t = t
 
     def flush(self):
-        """every row up to step t: weight, moments and target are then what the dense optimizer and ema_update_ hold.  A no-op
-        when nothing happened since the last flush.  Also where the findings of unchecked calls are raised."""
+        """every row up to step t: weight, the moments and a pair's target are then what the dense optimizer (and ema_update_)
+        hold.  A no-op when nothing happened since the last flush.  Also where the findings of unchecked calls are raised."""
         if self.flushed_at != self.t:
-            self._catchup(0, self.w.shape[0], self.t)
+            if self.stateful:
+                self._catchup(0, self.w.shape[0], self.t)
             self.flushed_at = self.t
             self.check()
+
+    def behind(self):
+        """steps the most outdated row lags behind (one device read)"""
+        return self.t - int(self.last.min()) if self.stateful else 0
+
+
+class RowLazyEmaTable(RowLazyTable):
+    """RowLazyTable's pair face under the name and with the constructor BUIR's optimizer uses"""
+
+    def __init__(self, weight, target, name, lr, l2, momentum, betas=(0.9, 0.999), eps=1e-8, max_lag=None):
+        super().__init__(weight, name, lr, l2, betas, eps, max_lag, target=target, momentum=momentum)
 
 
 class ScatterPlan:
