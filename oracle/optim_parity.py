@@ -29,6 +29,11 @@ Regimes (``case``; shapes, seeds and scales shared by tests/test_optim_power.py 
     C  hot rows        3K x 2.5K, B = 256, 24 steps, Zipf items and one hot user; D = 32; l2 = 0 / 1e-3
     D  saturated       3K x 2.5K, B = 256, 12 steps, D = 64, tables N(0, 0.7^2) as of a trained model: score differences
                        reach +-19, gradient elements span 1e-2 .. 2e-11 and v goes down to 4e-29
+    F  four rows per wave  70,001 x 140,003, B = 32,768, 4 steps (short last batch), uniform ids, tables N(0, 0.01^2) as A, lr 1e-3:
+                       32,768 user keys and 65,536 item keys per batch and tables of 70,001 / 140,003 rows are at or above the
+                       size (32,768) from which wr_lazy.hip's kernels hold four rows per wave; 140,003 rows are more than
+                       one stride (131,072) of its catch-up; windows of max_lag = 2 have 35,001 and 70,002 rows; D = 64 with
+                       l2 = 0 and D = 20 with l2 = 1e-3 (tests/test_hip_rowopt_wide.py)
     E  Adagrad / Adadelta  1.5K x 1.2K, B = 128, 14 steps (short last batch), uniform and Zipf, D = 64, 20; and Adadelta at
                        regime B's shape (E_gaps)
 
@@ -52,6 +57,10 @@ Measured floors (largest over the regime's variants):
     E_adagrad_zipf  (hot rows)               2.7e-1        3.52e-4     9.43e-4         2.84e-7    6.93e-5
     E_adadelta      (uniform and Zipf)       6.1e-2        9.97e-6     2.59e-5         3.44e-7    1.69e-7
     E_gaps          (Adadelta, B's shape)    2.9e-2        5.62e-6     1.15e-5         3.85e-7    1.30e-7
+    F     (l2 = 0, D = 64)                   7.6e-2        4.02e-6     6.10e-6         1.30e-5    3.04e-7
+    F_l2  (l2 = 1e-3, D = 20)                8.4e-2        2.05e-5     2.06e-5         1.30e-5    1.69e-6
+    F, SGD lr 1 with weight decay 1e-2 (TOL_F_SGD; fp32 C oracle against parity.bprmf_sgd_f64(l2=1e-2))
+                                             4.1e-2        3.25e-6     5.02e-6         -          1.33e-7
 
 The floors are not all roundings of a well-conditioned sum.  B and D (l2 = 0): a gradient element that is small by
 cancellation (p_d - n_d ~ 1e-5 of its terms) carries a relative fp32 error of 1e-3, and where sqrt(v) / sqrt(bc2) is within a
@@ -83,8 +92,16 @@ TOL = {
     "E_adagrad_zipf": {"update": 3e-03, "row": 8e-03, "state": 3e-06, "table": 6e-04},
     "E_adadelta": {"update": 8e-05, "row": 3e-04, "state": 3e-06, "table": 1e-05},
     "E_gaps": {"update": 5e-05, "row": 1e-04, "state": 4e-06, "table": 1e-05},
+    "F": {"update": 4e-05, "row": 5e-05, "state": 2e-04, "table": 1e-05},
+    "F_l2": {"update": 2e-04, "row": 2e-04, "state": 2e-04, "table": 2e-05},
 }
 TOL_LOSS = parity.TOL_TABLE                 # the bound on the losses, and the least bound on the table: unchanged
+
+# SGD with weight decay at regime F's shape (D = 64): hip_ops.LazyOptimizerState("SGD", lr, l2) against
+# parity.bprmf_sgd_f64(l2=...).  The decay moves every row by lr * l2 = 1e-2 of itself per step; a row's gradient step is
+# 0.5 * lr / B = 1.5e-5 of the table per occurrence — 1.5e-3 of the decay, and 60 times the tolerance on the row's update.
+F_SGD = {"lr": 1.0, "l2": 1e-2}
+TOL_F_SGD = {"update": 3e-5, "row": 5e-5}    # 8 x the floor of the fp32 C oracle (tests/test_optim_power.py)
 
 
 def _f(x):
@@ -124,6 +141,11 @@ def case(regime, D=64, zipf=False):
         rng = np.random.RandomState(400 + D)
         u, p, n = _ids(rng, nU, nI, steps * B, False, 0)
         scale = 0.7                          # score differences x ~ N(0, 5.5^2): |x| reaches about 20
+    elif regime == "F":
+        nU, nI, B, steps, lr = 70_001, 140_003, 32768, 4, 1e-3
+        rng = np.random.RandomState(600 + D)
+        u, p, n = _ids(rng, nU, nI, steps * B - B // 3, False, 0)
+        scale = 0.01
     elif regime == "E":                      # tests/test_hip_optimizers.py::test_sparse_fused_equals_dense_restatement
         nU, nI, B, steps, lr = 1_500, 1_200, 128, 14, None      # lr: by optimizer (E_LR)
         rng = np.random.RandomState(5 + D)
@@ -153,6 +175,8 @@ VARIANTS = {
     "E_adagrad_zipf": [("Adagrad", "E", D, True, 0.0) for D in (64, 20)],
     "E_adadelta": [("Adadelta", "E", D, zipf, 0.0) for D in (64, 20) for zipf in (False, True)],
     "E_gaps": [("Adadelta", "B", 64, False, 0.0)],
+    "F": [("Adam", "F", 64, False, 0.0)],
+    "F_l2": [("Adam", "F", 20, False, 1e-3)],
 }
 
 
@@ -162,6 +186,14 @@ def variant_reference(opt, regime, D, zipf, l2):
     c = case(regime, D, zipf)
     lr = c["lr"] if opt == "Adam" else E_LR[opt]
     return c, reference(opt, c["U0"], c["I0"], c["u"], c["p"], c["n"], c["B"], lr, l2, compact=l2 == 0.0)
+
+
+@functools.lru_cache(maxsize=None)
+def sgd_f_reference():
+    """(case data of regime F at D = 64, (U64, I64, losses) of SGD with F_SGD's weight decay on the whole tables): shared, do
+    not modify"""
+    c = case("F", 64)
+    return c, parity.bprmf_sgd_f64(c["U0"], c["I0"], c["u"], c["p"], c["n"], c["B"], F_SGD["lr"], l2=F_SGD["l2"])
 
 
 # --------------------------------------------------------------------------------------------------- float64 steps

@@ -95,23 +95,29 @@ def bpr_row_grads_f64(U, I, ub, pb, nbk):
     return ru, gu, ri, gi, float(np.mean(-np.log(GAMMA + s)))
 
 
-def bprmf_sgd_f64(U, I, u, p, n, batch, lr, n_steps=None, keep_steps=False):
+def bprmf_sgd_f64(U, I, u, p, n, batch, lr, n_steps=None, keep_steps=False, l2=0.0):
     """The reference loop's step (src/helpers/BaseRunner.py:194-200 with BPRMF.py:69-80 and loss.py:38; the semantics of
     oracle.bprmf_step_sgd, l2 = 0): strictly sequential batch-synchronous SGD steps, every gradient of a step from the tables
     before it, a short last batch allowed — in plain NumPy float64.  U, I: the tables the ids index (compact tables of the
-    touched rows for the large shapes; rows outside a batch have zero gradient and are not visited).  Returns (U64, I64,
-    losses[n_steps]) and, with keep_steps, a fourth value: the list of (U64, I64) copies after every step."""
+    touched rows for the large shapes; rows outside a batch have zero gradient and are not visited).  l2 != 0 (torch.optim.SGD's
+    weight_decay): dense, g += l2 * w on EVERY row of the tables handed in, so these must be the whole tables.  Returns (U64,
+    I64, losses[n_steps]) and, with keep_steps, a fourth value: the list of (U64, I64) copies after every step."""
     U, I = np.array(U, dtype=np.float64), np.array(I, dtype=np.float64)
     u, p, n = (np.asarray(a, dtype=np.int64) for a in (u, p, n))
     batch = int(batch)
     nb = (u.size + batch - 1) // batch if n_steps is None else int(n_steps)
-    lr = float(np.float32(lr))                       # the kernels and the C oracle take lr as a float
+    lr, l2 = float(np.float32(lr)), float(np.float32(l2))      # the kernels and the C oracle take lr and l2 as floats
     losses, kept = np.zeros(nb, np.float64), []
     for k in range(nb):
         ub, pb, nbk = u[k * batch:(k + 1) * batch], p[k * batch:(k + 1) * batch], n[k * batch:(k + 1) * batch]
         ru, gu, ri, gi, losses[k] = bpr_row_grads_f64(U, I, ub, pb, nbk)
+        if l2 != 0.0:                                # w -= lr * (g + l2 * w), the decay from the tables before the step
+            decay_u, decay_i = (lr * l2) * U, (lr * l2) * I
         U[ru] -= lr * gu
         I[ri] -= lr * gi
+        if l2 != 0.0:
+            U -= decay_u
+            I -= decay_i
         if keep_steps:
             kept.append((U.copy(), I.copy()))
     return (U, I, losses, kept) if keep_steps else (U, I, losses)

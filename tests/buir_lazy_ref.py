@@ -30,6 +30,24 @@ def make_case(n_rows, D, seed=0):
     return R.make_case(n_rows, D, -1, seed)
 
 
+# the wide and run-length cases of rowopt_ref (four rows per wave, the stride loop, run lengths): (n_rows, D, l2, momentum)
+WIDE_CASES = ((R.WIDE_ROWS, 64, 1e-3, 0.9), (R.WIDE_ROWS, 20, 0.0, 0.995))
+RUN_CASES = ((R.RUN_ROWS, 20, 1e-3, 0.9), (R.RUN_ROWS, 64, 0.0, 0.995), (R.RUN_ROWS, 100, 0.0, 0.9), (R.RUN_ROWS, 128, 1e-3, 0.995))
+WIDE_MUTANTS = R.WIDE_MUTANTS
+
+
+def make_wide_case(n_rows, D, seed=0):
+    return R.make_wide_case(n_rows, D, -1, seed)
+
+
+def make_any_case(case, seed=0):
+    """make_case / make_wide_case / rowopt_ref.make_run_case by the case tuple"""
+    n_rows, D = case[:2]
+    if case in RUN_CASES:
+        return R.make_run_case(n_rows, D, -1, seed)
+    return (make_wide_case if n_rows == R.WIDE_ROWS else make_case)(n_rows, D, seed)
+
+
 def _f(x):
     return float(F32(x))
 
@@ -43,7 +61,10 @@ def dense_loop(opt, W0, steps, lr, l2, mom, dtype=np.float64, betas=(0.9, 0.999)
     "sweep_unreplayed" the window sweep (max_lag = SWEEP_LAG) marks rows current without replaying them: the optimizer step AND
                        the target update of the lost (step, row) pairs do not happen;
     "replay_skip"      K22's: one zero-gradient optimizer step of row SKIP_ROW does not happen (its target update does);
-    "run_short"        K22's: the last position of the hot row's run is left out of its sum."""
+    "run_short"        K22's: the last position of the hot row's run is left out of its sum;
+    "fourth_row", "stride_tail", "window_offset"  the replay mutants of the wide cases (rowopt_ref.lost_of): the optimizer step
+                       AND the target update of the lost (step, row) pairs do not happen;
+    "run_trip"         K22's: a run whose length is a multiple of 64 loses its last 64 positions."""
     f = dtype
     W = np.array(W0, dtype=f)
     T = np.array(W0, dtype=f)
@@ -61,10 +82,13 @@ def dense_loop(opt, W0, steps, lr, l2, mom, dtype=np.float64, betas=(0.9, 0.999)
         lost = {SKIP_STEP: np.asarray([SKIP_ROW])}
     elif mutant == "sweep_unreplayed":
         lost = R.lost_by_unreplayed_sweep(steps, n_rows)
+    elif mutant in R.WIDE_MUTANTS:
+        lost = R.lost_of(mutant, steps, n_rows)
     stale_from, stale_to = R.GAP_USES[7]
     stale_T = None
     for t, (idx, src) in enumerate(steps, start=1):
-        G = R.grad_table(idx, src, n_rows, -1, f, drop_last_of=R.HOT_ROW if (mutant == "run_short" and t == R.HOT_STEPS[0]) else None)
+        G = R.grad_table(idx, src, n_rows, -1, f, drop_last_of=R.HOT_ROW if (mutant == "run_short" and t == R.HOT_STEPS[0]) else None,
+                         drop_trip=mutant == "run_trip")
         rows = lost.get(t)
         keep = None if rows is None else [a[rows].copy() for a in (W, m, v, T)]
         W_before = W.copy() if (mutant == "ema_before_step" and t == BEFORE_STEP) else None
@@ -89,7 +113,7 @@ def dense_loop(opt, W0, steps, lr, l2, mom, dtype=np.float64, betas=(0.9, 0.999)
         if mutant == "ema_skip" and t == SKIP_STEP:
             T_new[SKIP_ROW] = T[SKIP_ROW]
         T = T_new
-        if keep is not None and mutant == "sweep_unreplayed":
+        if keep is not None and mutant != "replay_skip":
             W[rows], m[rows], v[rows], T[rows] = keep
         if mutant == "ema_stale":
             if t == stale_from:

@@ -41,6 +41,34 @@ them; every one is asserted to be at least 4):
       the three momentum-0.9 cases only (see ``mutants``).
     SGD:  ema_skip 19 x (3.87e-3), ema_before_step 263 x (5.26e-2), ema_stale 5.0 x (9.98e-4, l2 != 0), sweep_unreplayed 1785 x
       (3.57e-1) on t_update; replay_skip 11 x (row 2.22e-3, l2 != 0), run_short 182 x (row 3.64e-2).
+
+Wide and run-length cases (buir_lazy_ref.WIDE_CASES / RUN_CASES: the inputs of rowopt_ref's, 140,003 rows — four rows per wave,
+more than one stride of the catch-up — and runs of exactly 1 .. 300 positions; tests/test_hip_rowopt_wide.py).  TOL_WIDE by the
+same rule over these cases, a key of its own; TOL above is unchanged.  Floors:
+
+    Adam (n_rows, D, l2, momentum)     update/table (target)  update_err  row_update_err  t_update_err  t_row_update_err  state_err
+    (140003, 64, 0.001, 0.9)           1.1e-02  (3.2e-03 )    2.11e-05    2.11e-05        5.87e-05      5.92e-05          1.34e-05
+    (140003, 20, 0.0, 0.995)           1.0e-02  (1.9e-04 )    1.95e-05    2.54e-05        1.78e-03      2.20e-02          1.31e-05
+    (1000, 20, 0.001, 0.9)             4.6e-03  (6.6e-04 )    2.04e-05    2.04e-05        1.25e-04      1.25e-04          1.21e-05
+    (1000, 64, 0.0, 0.995)             4.8e-03  (3.6e-05 )    2.02e-05    2.02e-05        3.47e-03      3.47e-03          1.32e-05
+    (1000, 100, 0.0, 0.9)              5.0e-03  (7.2e-04 )    2.05e-05    2.05e-05        1.34e-04      1.34e-04          1.32e-05
+    (1000, 128, 0.001, 0.995)          3.9e-03  (3.0e-05 )    2.10e-05    2.10e-05        3.54e-03      3.54e-03          1.29e-05
+    SGD
+    (140003, 64, 0.001, 0.9)           5.3e-01  (1.7e-01 )    4.09e-07    7.83e-06        1.08e-06      3.69e-05          -
+    (140003, 20, 0.0, 0.995)           4.7e-01  (9.7e-03 )    2.38e-07    2.67e-06        3.59e-05      1.55e-03          -
+    (1000, 20, 0.001, 0.9)             7.8e-01  (1.2e-01 )    4.39e-07    1.88e-06        8.90e-07      1.91e-05          -
+    (1000, 64, 0.0, 0.995)             6.5e-01  (4.4e-03 )    4.50e-07    1.53e-06        2.63e-05      3.39e-04          -
+    (1000, 100, 0.0, 0.9)              8.3e-01  (1.2e-01 )    4.18e-07    1.49e-06        8.62e-07      1.39e-05          -
+    (1000, 128, 0.001, 0.995)          8.2e-01  (6.1e-03 )    2.89e-07    2.49e-06        1.72e-05      3.36e-04          -
+    TOL_WIDE  Adam: update 8 x 2.11e-5 -> 2e-4, row 8 x 2.54e-5 -> 3e-4, state 8 x 1.34e-5 -> 2e-4, t_update 0.9: 8 x 1.34e-4 ->
+      2e-3, 0.995: 8 x 3.54e-3 -> 3e-2, t_row 0.9: 8 x 1.34e-4 -> 2e-3, 0.995: 8 x 2.20e-2 -> 2e-1;  SGD: update 8 x 4.50e-7 -> 4e-6,
+      row 8 x 7.83e-6 -> 7e-5, t_update 0.9: 8 x 1.08e-6 -> 9e-6, 0.995: 8 x 3.59e-5 -> 3e-4, t_row 0.9: 8 x 3.69e-5 -> 3e-4, 0.995:
+      8 x 1.55e-3 -> 2e-2.
+Power of the wide cases (``wide_mutants``; every one is asserted to exceed its tolerance at least 4 times; smallest figures):
+    Adam, on row: fourth_row 7.06e-1 (2,354 x), stride_tail 7.06e-1, window_offset 3.56e-1 (1,188 x), run_trip 1.83 (6,114 x).
+    SGD with decay, on row: fourth_row 1.24e-1 (1,774 x), stride_tail 1.22e-1, window_offset 3.84e-2 (549 x); without decay the
+      online row does not move without a gradient and the target's rows show them, on t_row at momentum 0.995: fourth_row
+      8.31e-1 (42 x), stride_tail 8.31e-1, window_offset 4.98e-1 (25 x); run_trip on row 6.97e-1 (9,954 x).
 """
 import functools
 import math
@@ -57,6 +85,9 @@ from oracle import parity  # noqa: E402
 # the tolerances tests/test_hip_buir_lazy.py imports
 TOL = {"Adam": {"update": 3e-4, "row": 4e-4, "state": 2e-4, "t_update": {0.9: 3e-4, 0.995: 9e-3}, "t_row": {0.9: 2e-3, 0.995: 2e-1}},
        "SGD": {"update": 5e-6, "row": 2e-4, "t_update": {0.9: 6e-6, 0.995: 2e-4}, "t_row": {0.9: 3e-4, 0.995: 9e-3}}}
+# ... and tests/test_hip_rowopt_wide.py: the wide and run-length cases (buir_lazy_ref.WIDE_CASES, RUN_CASES)
+TOL_WIDE = {"Adam": {"update": 2e-4, "row": 3e-4, "state": 2e-4, "t_update": {0.9: 2e-3, 0.995: 3e-2}, "t_row": {0.9: 2e-3, 0.995: 2e-1}},
+            "SGD": {"update": 4e-6, "row": 7e-5, "t_update": {0.9: 9e-6, 0.995: 3e-4}, "t_row": {0.9: 3e-4, 0.995: 2e-2}}}
 POWER = 4.0                                  # a wrong step exceeds its tolerance at least this many times
 
 
@@ -209,6 +240,88 @@ def test_every_wrong_step_of_the_issue_is_exercised():
             assert {c[0] for c in mine} == {1000, 20000} and 1e-3 in {c[2] for c in mine}, (opt, m)
             assert (m in ("ema_stale", "replay_skip") and opt == "SGD") or 0.0 in {c[2] for c in mine}, (opt, m)
     assert "ema_stale" not in mutants("SGD", B.CASES[0]) and "ema_stale" in mutants("SGD", B.CASES[1])
+
+
+# ------------------------------------------------------------------------------------------------ wide and run-length cases
+@functools.lru_cache(maxsize=None)
+def wide_runs(opt, case):
+    """(W0, steps, float64 run, run(dtype, mutant)) of one wide or run-length case: computed once, shared, never modified"""
+    n_rows, D, l2, mom = case
+    W0, steps = B.make_any_case(case)
+    run = lambda dtype, mutant=None: B.dense_loop(opt, W0, steps, B.LR[opt], l2, mom, dtype, mutant=mutant)   # noqa: E731
+    return W0, steps, run(np.float64), run
+
+
+def tol_wide(opt, name, mom):
+    t = TOL_WIDE[opt][name]
+    return t[mom] if isinstance(t, dict) else t
+
+
+def test_wide_cases_are_those_of_the_single_table():
+    R = B.R
+    assert B.WIDE_CASES == ((140003, 64, 1e-3, 0.9), (140003, 20, 0.0, 0.995)) and {c[1] for c in B.RUN_CASES} == {20, 64, 100, 128}
+    for cases in (B.WIDE_CASES, B.RUN_CASES):
+        assert {c[2] for c in cases} == {0.0, 1e-3} and {c[3] for c in cases} == {0.9, 0.995}
+    for case in B.WIDE_CASES + B.RUN_CASES:
+        W0, steps = B.make_any_case(case)
+        W1, steps1 = R.make_any_case((case[0], case[1], -1, 0.0) if case in B.WIDE_CASES else
+                                     [c for c in R.RUN_CASES if c[1] == case[1]][0])
+        assert np.array_equal(W0, W1) and all(np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]) for a, b in zip(steps, steps1))
+
+
+def wide_mutants(opt, case):
+    """(mutant, the measure that sees it).  The replay mutants lose optimizer steps and target updates of rows without a
+    gradient: the online table shows them under Adam and under weight decay; under SGD without decay such a row does not
+    move and only its target (which still follows the row) can show them."""
+    if case in B.RUN_CASES:
+        return [("run_trip", "row")]
+    return [(m, "row" if (opt == "Adam" or case[2] != 0) else "t_row") for m in B.WIDE_MUTANTS]
+
+
+@pytest.mark.parametrize("opt", ["Adam", "SGD"])
+def test_wide_tolerances_are_eight_times_the_largest_floor(opt):
+    cases = B.WIDE_CASES + B.RUN_CASES
+    floors = []
+    for case in cases:
+        W0, _, ref, run = wide_runs(opt, case)
+        fig = figures(W0, ref, run(np.float32))
+        print("floor %s %s: update/table %.1e (target %.1e) update_err %.2e row_update_err %.2e t_update_err %.2e t_row_update_err "
+              "%.2e state_err %.2e" % (opt, case, fig["update_over_table"], fig["t_update_over_table"], fig["update"], fig["row"],
+                                       fig["t_update"], fig["t_row"], fig.get("state", 0.0)))
+        floors.append(fig)
+    wrong = []
+    assert set(TOL_WIDE[opt]) == set(TOL[opt])
+    for name, t in TOL_WIDE[opt].items():
+        for mom in (sorted(t) if isinstance(t, dict) else [None]):
+            worst = max(f[name] for f, c in zip(floors, cases) if mom is None or c[3] == mom)
+            print("TOL_WIDE %s %s %s: 8 x %.2e = %.1e -> %.0e" % (opt, name, mom or "", worst, 8 * worst, _round_up_one_digit(8 * worst)))
+            if not (math.isclose(tol_wide(opt, name, mom), _round_up_one_digit(8 * worst), rel_tol=1e-9)
+                    and 4 * worst < tol_wide(opt, name, mom)):
+                wrong.append((opt, name, mom, worst))
+    assert not wrong, wrong
+
+
+@pytest.mark.parametrize("opt", ["Adam", "SGD"])
+@pytest.mark.parametrize("case", B.WIDE_CASES + B.RUN_CASES)
+def test_wide_wrong_steps_exceed_the_tolerances(opt, case):
+    W0, _, ref, run = wide_runs(opt, case)
+    weak = []
+    for mutant, name in wide_mutants(opt, case):
+        fig = figures(W0, ref, run(np.float32, mutant))
+        bound = tol_wide(opt, name, case[3])
+        print("power %s %s %s: %s %.2e = %.1f x tol %.0e | update %.2e row %.2e t_update %.2e t_row %.2e" % (
+            opt, case, mutant, name, fig[name], fig[name] / bound, bound, fig["update"], fig["row"], fig["t_update"], fig["t_row"]))
+        if not fig[name] > POWER * bound:
+            weak.append((mutant, name, fig[name], bound))
+    assert not weak, (opt, case, weak)
+
+
+def test_every_wide_wrong_step_is_exercised():
+    for opt in ("Adam", "SGD"):
+        seen = {m for case in B.WIDE_CASES + B.RUN_CASES for m, _ in wide_mutants(opt, case)}
+        assert seen == set(B.WIDE_MUTANTS) | {"run_trip"}, opt
+        for case in B.WIDE_CASES:                                 # a pair is always stateful: every wide case shows every one
+            assert [m for m, _ in wide_mutants(opt, case)] == list(B.WIDE_MUTANTS)
 
 
 # ------------------------------------------------------------------------------------------------ the interface, without a GPU

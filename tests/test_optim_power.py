@@ -20,6 +20,9 @@ Which regime sees what (SEES; everything is printed, the listed ones are asserte
   - Adadelta replayed one rho decay short, every row: E_adadelta and E_gaps.  One row, once: E_adadelta only — in E_gaps the
     state has decayed by rho^150 before the row's next update, so one decay more or less is invisible there (1.1e-5, the floor).
   - Adagrad state not accumulated for one row in one step (the row's second): both Adagrad regimes.
+  - regime F (the shape at which wr_lazy.hip's kernels hold four rows per wave) sees every Adam wrong step, smallest
+    row_update_err: one missed replay step 1.99e-1 (F, tolerance 5e-5), one missing occurrence 1.36e-2 (F_l2, tolerance 2e-4).
+    SGD with weight decay at that shape: one missed decay step of one row 2.5e-1 of the row's update (tolerance 5e-5).
 """
 import functools
 import math
@@ -85,6 +88,42 @@ def test_tolerances_are_eight_times_the_largest_floor(key):
     assert math.isclose(op.TOL[key]["table"], max(op.TOL_LOSS, _round_up_one_digit(8 * worst)), rel_tol=1e-9), (key, worst)
     assert 4 * worst < op.TOL[key]["table"]
     assert op.TOL_LOSS == 1e-5 and all(4 * f["loss_err"] < op.TOL_LOSS for f in floors)
+
+
+@functools.lru_cache(maxsize=None)
+def _sgd_f_run(skip=None):
+    """the fp32 C oracle's SGD with weight decay at regime F's shape; skip = (k, user row): the row is not in batch k and its
+    decay of that step does not happen (a missed replay)"""
+    c, _ = op.sgd_f_reference()
+    U, I = np.array(c["U0"]), np.array(c["I0"])
+    B, losses = c["B"], []
+    for k in range(c["steps"]):
+        sl = slice(k * B, (k + 1) * B)
+        keep = U[skip[1]].copy() if skip is not None and k == skip[0] else None
+        losses.append(oracle.bprmf_step_sgd(U, I, c["u"][sl], c["p"][sl], c["n"][sl], op.F_SGD["lr"], op.F_SGD["l2"]))
+        if keep is not None:
+            U[skip[1]] = keep
+    return U, I, np.asarray(losses)
+
+
+def test_sgd_decay_tolerances_at_regime_f_are_eight_times_the_floor():
+    """SGD with weight decay at regime F's shape (tests/test_hip_rowopt_wide.py): TOL_F_SGD from the fp32 C oracle against
+    parity.bprmf_sgd_f64(l2=...), and one missed decay step of one row exceeds it"""
+    c, ref = op.sgd_f_reference()
+    U, I, losses = _sgd_f_run()
+    fig = parity.sgd_run_errors(c["U0"], c["I0"], ref, U, I)
+    loss_err = parity.table_err(losses, ref[2])
+    print("floor F SGD lr %g l2 %g: update/table %.1e update_err %.2e row_update_err %.2e table_err %.2e loss_err %.2e" % (
+        op.F_SGD["lr"], op.F_SGD["l2"], fig["update_over_table"], fig["update_err"], fig["row_update_err"], fig["table_err"], loss_err))
+    for name, key in (("update", "update_err"), ("row", "row_update_err")):
+        assert math.isclose(op.TOL_F_SGD[name], _round_up_one_digit(8 * fig[key]), rel_tol=1e-9), (name, fig[key])
+        assert 4 * fig[key] < op.TOL_F_SGD[name]
+    assert 4 * fig["table_err"] < op.TOL_LOSS and 4 * loss_err < op.TOL_LOSS
+    k, row = _victim(c["u"], c["B"], c["steps"], "replay_skip")
+    U, I, _ = _sgd_f_run((k + 1, row))
+    mut = parity.sgd_run_errors(c["U0"], c["I0"], ref, U, I)
+    print("F SGD replay_skip: update_err %.2e row_update_err %.2e (tol %.0e)" % (mut["update_err"], mut["row_update_err"], op.TOL_F_SGD["row"]))
+    assert mut["row_update_err"] > op.TOL_F_SGD["row"]
 
 
 def test_eps_regime_is_the_eps_regime():
@@ -245,6 +284,8 @@ SEES = {
     "E_adagrad_zipf": ("state_skip", "missing_occurrence"),
     "E_adadelta": ("decay_short", "decay_short_one_row", "missing_occurrence"),
     "E_gaps": ("decay_short", "missing_occurrence"),
+    "F": ("eps_under_sqrt", "eps_before_bc2", "bias_t_plus_1", "bias_t_minus_1", "replay_skip", "missing_occurrence"),
+    "F_l2": ("eps_under_sqrt", "eps_before_bc2", "bias_t_plus_1", "bias_t_minus_1", "missing_occurrence", "decoupled_decay"),
 }
 
 
