@@ -1266,6 +1266,36 @@ int32_t wr_softmax_ce_loss_grad(const float *Q, int64_t B, const float *E, int64
                                 int64_t first_class, float weight, float *loss, int32_t accumulate, float *gQ, float *gE,
                                 int32_t *err_word, void *workspace, int64_t workspace_bytes, void *stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * K27 — one-layer GRU over left-aligned, zero-padded histories with a length per row (whisprrec_amd/gru4rec.py, --gru_native 1),
+ * forward and backward, fp32.  x [B, T, E], lengths int64 [B], w_ih [3H, E], w_hh [3H, H], b_ih, b_hh [3H]; torch's cell and
+ * gate order (r, z, n), h_0 = 0:
+ *   r = sigmoid(W_ir x + b_ir + W_hr h + b_hr)      z = sigmoid(W_iz x + b_iz + W_hz h + b_hz)
+ *   n = tanh(W_in x + b_in + r * (W_hn h + b_hn))   h' = (1 - z) * n + z * h
+ *   - Row b takes its first len_b = min(max(lengths[b], 0), T) steps and is frozen afterwards: h_last[b] [H] is its state after
+ *     step len_b - 1.  A length of 0 (or below) gives h_last[b] = 0 and no gradient from that row; a length above T acts as T.
+ *     x[b, t, :] is never read for t >= len_b (it may hold anything, NaN included).
+ *   - Supported (wr_gru_supported): E, H in {32, 64} in any combination, T >= 1 without an upper limit (x_t is streamed),
+ *     1 <= B <= 2^24.  Anything else, a NULL or misaligned (16 B) pointer or a short workspace is refused (WR_E_*) with the
+ *     numbers before any launch.
+ *   - wr_gru_fwd: one launch; both weight matrices and the h of a 16-row tile stay on chip for the whole walk.  hs != NULL:
+ *     every step's h_t is stored to hs [B, T, H] (the frozen value for t >= len_b), the one activation wr_gru_bwd reads;
+ *     hs == NULL (inference): nothing but h_last is written.
+ *   - wr_gru_bwd: g_last [B, H] -> gx [B, T, E] (exactly zero for t >= len_b), g_w_ih, g_w_hh, g_b_ih, g_b_hh, all fully
+ *     written.  The gates are recomputed from x_t and hs[t - 1].  Two launches: the reverse walk keeps the parameter gradients of
+ *     its tiles (tiles w, w + G, ..., G = min(ceil(B / 16), 256)) in registers across all t and writes them once to its own slab
+ *     of the workspace; the second launch folds the slabs in workgroup order.  No float atomics: same inputs, same bits.
+ *   - workspace >= wr_gru_workspace_bytes(B, T, E, H), 16-byte aligned (backward only): 256 slabs of 3H (E + H) + 6H floats,
+ *     independent of B and T.  No host round trip, no allocation. */
+int32_t wr_gru_supported(int32_t E, int32_t H, int32_t T);
+int64_t wr_gru_workspace_bytes(int64_t B, int32_t T, int32_t E, int32_t H);
+int32_t wr_gru_fwd(const float *x, const int64_t *lengths, const float *w_ih, const float *w_hh, const float *b_ih,
+                   const float *b_hh, int64_t B, int32_t T, int32_t E, int32_t H, float *h_last, float *hs, void *stream);
+int32_t wr_gru_bwd(const float *x, const int64_t *lengths, const float *w_ih, const float *w_hh, const float *b_ih,
+                   const float *b_hh, const float *hs, const float *g_last, int64_t B, int32_t T, int32_t E, int32_t H, float *gx,
+                   float *g_w_ih, float *g_w_hh, float *g_b_ih, float *g_b_hh, void *workspace, int64_t workspace_bytes,
+                   void *stream);
+
 #ifdef __cplusplus
 }
 #endif

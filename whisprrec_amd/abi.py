@@ -254,6 +254,11 @@ SIGNATURES = {
     "wr_softmax_ce_workspace_bytes": (c_i64, [c_i64, c_i64, c_i32]),
     "wr_softmax_ce_loss_grad": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i32, c_vp, c_i64, c_f32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp,
                                         c_i64, c_vp]),
+    "wr_gru_supported": (c_i32, [c_i32, c_i32, c_i32]),
+    "wr_gru_workspace_bytes": (c_i64, [c_i64, c_i32, c_i32, c_i32]),
+    "wr_gru_fwd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    "wr_gru_bwd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp,
+                           c_vp, c_i64, c_vp]),
 }
 
 

@@ -2015,6 +2015,98 @@ def ti_attention(q, k, v, times, min_interval, time_k, time_v, n_heads, time_max
     return _TiAttention.apply(q, k, v, time_k, time_v, times, min_interval, n_heads, time_max, err_word)
 
 
+# --------------------------------------------------------------------------------------------------------------- GRU (K27)
+def gru_supports(E, H, T):
+    """shapes wr_gru_fwd / _bwd take (wr_gru_supported): E, H in {32, 64} in any combination, T >= 1"""
+    return bool(abi.lib().wr_gru_supported(int(E), int(H), int(T)))
+
+
+def gru_workspace_bytes(B, T, E, H):
+    return abi.check_size(abi.lib().wr_gru_workspace_bytes(int(B), int(T), int(E), int(H)), "wr_gru_workspace_bytes")
+
+
+def _gru_args(x, lengths, w_ih, w_hh, b_ih, b_hh):
+    """the argument checks of gru_fwd / gru_bwd -> (B, T, E, H)"""
+    _req(x, torch.float32, "x", 3)
+    _req(lengths, torch.int64, "lengths", 1)
+    _req(w_ih, torch.float32, "w_ih", 2)
+    _req(w_hh, torch.float32, "w_hh", 2)
+    _req(b_ih, torch.float32, "b_ih", 1)
+    _req(b_hh, torch.float32, "b_hh", 1)
+    B, T, E = (int(s) for s in x.shape)
+    H = int(w_hh.shape[1])
+    if (lengths.numel() != B or tuple(w_ih.shape) != (3 * H, E) or tuple(w_hh.shape) != (3 * H, H) or b_ih.numel() != 3 * H
+            or b_hh.numel() != 3 * H):
+        raise ValueError("x must be [B, T, E], lengths [B], w_ih [3H, E], w_hh [3H, H], b_ih and b_hh [3H] (got %s, %s, %s, %s, %s, %s)"
+                         % tuple(tuple(t.shape) for t in (x, lengths, w_ih, w_hh, b_ih, b_hh)))
+    if B < 1 or not gru_supports(E, H, T):
+        raise abi.WhisprRecHipError("gru does not support B=%d T=%d E=%d H=%d (E, H in {32, 64}, T >= 1, B >= 1)" % (B, T, E, H))
+    return B, T, E, H
+
+
+def gru_fwd(x, lengths, w_ih, w_hh, b_ih, b_hh, save_hs=False):
+    """One-layer GRU (torch's cell, gates r, z, n, h_0 = 0) over left-aligned histories x [B, T, E] in one launch of wr_gru_fwd ->
+    (h_last [B, H], hs): row b takes its first clamp(lengths[b], 0, T) steps, h_last[b] is its state after them (zeros for a
+    length of 0); x[b, t, :] is never read at t >= lengths[b].  save_hs: every step's state is also stored, hs [B, T, H] (what
+    gru_bwd reads); otherwise hs is None and nothing but h_last is allocated or written."""
+    B, T, E, H = _gru_args(x, lengths, w_ih, w_hh, b_ih, b_hh)
+    h_last = torch.empty((B, H), dtype=torch.float32, device=x.device)
+    hs = torch.empty((B, T, H), dtype=torch.float32, device=x.device) if save_hs else None
+    abi.check(abi.lib().wr_gru_fwd(_p(x), _p(lengths), _p(w_ih), _p(w_hh), _p(b_ih), _p(b_hh), B, T, E, H, _p(h_last), _p(hs),
+                                   _stream()), "wr_gru_fwd")
+    return h_last, hs
+
+
+def gru_bwd(x, lengths, w_ih, w_hh, b_ih, b_hh, hs, g_last):
+    """The gradients of gru_fwd's h_last for g_last [B, H] (wr_gru_bwd, two launches; the gates are recomputed from x and hs):
+    (gx [B, T, E], g_w_ih, g_w_hh, g_b_ih, g_b_hh).  gx is exactly zero at t >= lengths[b].  No float atomics: same inputs, same
+    bits."""
+    B, T, E, H = _gru_args(x, lengths, w_ih, w_hh, b_ih, b_hh)
+    _req(hs, torch.float32, "hs", 3)
+    _req(g_last, torch.float32, "g_last", 2)
+    if tuple(hs.shape) != (B, T, H) or tuple(g_last.shape) != (B, H):
+        raise ValueError("hs must be [B, T, H] = %s and g_last [B, H] (got %s and %s)"
+                         % ((B, T, H), tuple(hs.shape), tuple(g_last.shape)))
+    gx = torch.empty_like(x)
+    g_w_ih, g_w_hh, g_b_ih, g_b_hh = (torch.empty_like(t) for t in (w_ih, w_hh, b_ih, b_hh))
+    ws = workspace(x.device, "gru").get(gru_workspace_bytes(B, T, E, H))
+    abi.check(abi.lib().wr_gru_bwd(_p(x), _p(lengths), _p(w_ih), _p(w_hh), _p(b_ih), _p(b_hh), _p(hs), _p(g_last), B, T, E, H,
+                                   _p(gx), _p(g_w_ih), _p(g_w_hh), _p(g_b_ih), _p(g_b_hh), _p(ws), ws.numel(), _stream()),
+              "wr_gru_bwd")
+    return gx, g_w_ih, g_w_hh, g_b_ih, g_b_hh
+
+
+gru_stats = {"calls": 0, "hs_bytes": 0}      # of the last gru_last call: the bytes of the step states it kept (0: none)
+
+
+class _GruLast(torch.autograd.Function):
+    """wr_gru_fwd / _bwd: saves the inputs and hs [B, T, H], the one activation"""
+
+    @staticmethod
+    def forward(ctx, x, w_ih, w_hh, b_ih, b_hh, lengths, save_hs):
+        args = [t.detach().contiguous() for t in (x, w_ih, w_hh, b_ih, b_hh)]
+        h_last, hs = gru_fwd(args[0], lengths, *args[1:], save_hs=save_hs)
+        gru_stats["calls"] += 1
+        gru_stats["hs_bytes"] = 0 if hs is None else hs.numel() * hs.element_size()
+        if hs is not None:
+            ctx.save_for_backward(lengths, hs, *args)
+        return h_last
+
+    @staticmethod
+    def backward(ctx, g_last):
+        lengths, hs, x, w_ih, w_hh, b_ih, b_hh = ctx.saved_tensors
+        gx, g_w_ih, g_w_hh, g_b_ih, g_b_hh = gru_bwd(x, lengths, w_ih, w_hh, b_ih, b_hh, hs, g_last.contiguous())
+        return gx, g_w_ih, g_w_hh, g_b_ih, g_b_hh, None, None
+
+
+def gru_last(x, lengths, w_ih, w_hh, b_ih, b_hh):
+    """gru_fwd under autograd: h_last [B, H] whose backward hands back the kernel's gx and the four parameter gradients.  Under
+    torch.no_grad(), or when neither x nor a parameter requires grad, no step state is kept (gru_stats["hs_bytes"] == 0)."""
+    lengths = _idx64(lengths, "lengths")
+    save_hs = torch.is_grad_enabled() and any(t.requires_grad for t in (x, w_ih, w_hh, b_ih, b_hh))
+    return _GruLast.apply(x, w_ih, w_hh, b_ih, b_hh, lengths, save_hs)
+
+
 def sgd_dense(tab, grad, lr, l2=0.0, stamp=None, step_id=0):
     abi.check(abi.lib().wr_sgd_dense(_p(_req(tab, torch.float32, "tab", 2)), tab.shape[0], tab.shape[1],
                                      _p(_req(grad, torch.float32, "grad", 2)), _p(stamp), step_id, lr, l2, _stream()),

@@ -1,4 +1,4 @@
-"""``--train_loss softmax`` for SASRec and TiSASRec: softmax cross-entropy of the last-position query against the whole item
+"""``--train_loss softmax`` for SASRec, TiSASRec and GRU4Rec: softmax cross-entropy of the last-position query against the whole item
 catalogue, instead of the reference's BPRLoss against one sampled negative (SASRec.py / TiSASRec.py ``loss``).
 
 The stock path (``--softmax_native 0``) is what defines the feature:
