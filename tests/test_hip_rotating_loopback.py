@@ -52,9 +52,14 @@ class LoopbackTransport:
 
     def all_gather(self, t):
         torch.cuda.current_stream().synchronize()
+        # every rank is a thread with a stream of its own: a copy is finished, not merely queued, before another rank may read
+        # it (first barrier) or its owner may drop it (second barrier)
+        cur = torch.cuda.current_stream()
         self.sh.slots[self.rank] = t.clone()
+        cur.synchronize()
         self.sh.barrier.wait()
         out = [self.sh.slots[r].clone() for r in range(self.world)]
+        cur.synchronize()
         self.sh.barrier.wait()
         return out
 

@@ -1,13 +1,27 @@
 """Device negative sampler (wr_sample_negatives) vs its NumPy restatement in the oracle: bit-exact indices, the
 reference's rule (range [1, n_items), never an item of the user's train set — src/models/BaseModel.py:167-177), and
-reproducibility."""
+reproducibility.  The restatement is the project's own generator, so equality alone would pass a biased rule on both sides:
+the device's own output also faces the distribution battery of tests/epoch_prep_ref.py (uniform over the allowed items, a
+uniform order; |z| <= 4.9 per statistic, calibrated in tests/test_epoch_prep_contract.py).  Run with -rP for every z."""
+import functools
+import os
+import sys
+
 import numpy as np
 import pytest
 import torch
 
 import oracle
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import epoch_prep_ref as E  # noqa: E402
+
 pytestmark = pytest.mark.gpu
+
+
+def _inside(name, z, extra=""):
+    print("z %-72s %+8.2f %s" % (name, z, extra))
+    assert abs(z) <= E.BOUND, "%s: z = %.2f outside %.1f sigma" % (name, z, E.BOUND)
 
 
 def _csr(sets, nU):
@@ -45,25 +59,70 @@ def test_matches_oracle_bit_exact(g3, dtype):
     assert not torch.equal(a, b)
 
 
-def test_large_uniformity_and_exclusion():
-    from whisprrec_amd import hip_ops
-    dev = torch.device("cuda:0")
+@functools.lru_cache(maxsize=None)
+def _large_case():
+    """2,000 users with 1 to 60 clicked of 5,000 items, 1 M rows; the restatement of the first 200,000, computed once"""
     rng = np.random.RandomState(0)
     nU, nI, n = 2000, 5000, 1_000_000
     sets = {u: set(rng.randint(0, nI, rng.randint(1, 60)).tolist()) for u in range(nU)}
     ptr, idx = _csr(sets, nU)
     users = rng.randint(0, nU, n)
-    neg, err = hip_ops.sample_negatives(torch.from_numpy(users).to(dev), nU, nI, torch.from_numpy(ptr).to(dev),
-                                        torch.from_numpy(idx).to(dev), 1, 0)
-    got = neg.cpu().numpy()
+    ref = oracle.sample_negatives_counter(users[:200_000], nI, ptr, idx, 1, 0)
+    ref.setflags(write=False)
+    return nU, nI, n, sets, ptr, idx, users, ref
+
+
+@pytest.mark.parametrize("dtype", [torch.int64, torch.int32])
+@pytest.mark.parametrize("form", ["lists", "pairs"])
+def test_large_uniformity_and_exclusion(form, dtype):
+    from whisprrec_amd import hip_ops
+    dev = torch.device("cuda:0")
+    nU, nI, n, sets, ptr, idx, users, ref = _large_case()
+    tptr, tidx = torch.from_numpy(ptr).to(dev), torch.from_numpy(idx).to(dev)
+    tu = torch.from_numpy(users).to(dev).to(dtype)
+    if form == "pairs":
+        neg, err = hip_ops.sample_negatives(tu, nU, nI, None, None, 1, 0, pairs=hip_ops.pair_set(tptr, tidx, nU))
+    else:
+        neg, err = hip_ops.sample_negatives(tu, nU, nI, tptr, tidx, 1, 0)
+    assert neg.dtype == dtype
+    got = neg.cpu().numpy().astype(np.int64)
     assert int(err.item()) == 0 and got.min() >= 1 and got.max() < nI
     # exclusion, vectorised: (user, item) pairs of the train set never appear
     train_keys = np.concatenate([np.full(ptr[u + 1] - ptr[u], u, np.int64) * nI + idx[ptr[u]:ptr[u + 1]] for u in range(nU)])
     assert not np.isin(users.astype(np.int64) * nI + got, train_keys).any()
+    assert E.forbidden(got, users, sets, nI) == 0
     counts = np.bincount(got, minlength=nI)[1:]
     assert abs(counts.mean() - n / (nI - 1)) < 1e-6 and counts.std() / counts.mean() < 0.15   # flat histogram
-    sample = slice(0, 3000)
-    assert np.array_equal(got[sample], oracle.sample_negatives_counter(users[sample], nI, ptr, idx, 1, 0))
+    # ... and against its expectation under the rule (each row uniform over its user's allowed items), which needs no oracle
+    # run: the Poisson noise of this case alone is a std / mean of 0.0707
+    _inside("device %s %s 1 M rows item_chi2" % (form, str(dtype)[6:]), E.item_chi2(got, users, sets, nI),
+            "std / mean %.4f" % (counts.std() / counts.mean()))
+    assert np.array_equal(got[:len(ref)], ref)
+
+
+@pytest.mark.parametrize("percent", [20, 80, 0])
+def test_one_user_is_uniform_over_the_allowed_items(percent):
+    """200,000 rows of one user who clicked 20 % / 80 % / none of 50 items: uniform over the allowed ones, and unrelated between
+    epochs and between seeds (the share of equal draws is 1 / |allowed|)"""
+    from whisprrec_amd import hip_ops
+    dev = torch.device("cuda:0")
+    nI, n = 51, 200_000
+    clicked = set(np.random.RandomState(1).permutation(np.arange(1, nI))[:percent * (nI - 1) // 100].tolist())
+    allowed = np.array(sorted(set(range(1, nI)) - clicked))
+    ptr, idx = _csr({0: clicked}, 1)
+    users = np.zeros(n, np.int64)
+    tu, tptr, tidx = torch.from_numpy(users).to(dev), torch.from_numpy(ptr).to(dev), torch.from_numpy(idx).to(dev)
+    draws = []
+    for seed, epoch in ((3407, 0), (3407, 1), (3408, 0)):
+        neg, err = hip_ops.sample_negatives(tu, 1, nI, tptr, tidx, seed, epoch)
+        got = neg.cpu().numpy()
+        assert int(err.item()) == 0 and E.forbidden(got, users, {0: clicked}, nI) == 0
+        assert np.array_equal(got, E.sample_negatives_counter(users, nI, ptr, idx, seed, epoch))
+        draws.append(got)
+    tag = "device user %d%% clicked" % percent
+    _inside(tag + " user_chi2", E.user_chi2(draws[0], allowed))
+    _inside(tag + " equal_rate epochs 0, 1", E.equal_rate(draws[0], draws[1], len(allowed)))
+    _inside(tag + " equal_rate seeds 3407, 3408", E.equal_rate(draws[0], draws[2], len(allowed)))
 
 
 def test_user_who_clicked_everything_is_flagged():
@@ -80,7 +139,9 @@ def test_user_who_clicked_everything_is_flagged():
 
 # ----------------------------------------------------------------------------------------------- epoch shuffle
 @pytest.mark.parametrize("dtype", [torch.int64, torch.int32])
-@pytest.mark.parametrize("n", [1, 2, 3, 17, 1000, 4097, 65536, 100003])
+# 512 / 8192 / 131072: exact powers of two on an odd number of bits; 513 / 8193 / 131073: 2^k + 1 on an even number, the longest
+# cycle walks (the domain is almost 2 n)
+@pytest.mark.parametrize("n", [1, 2, 3, 17, 511, 512, 513, 1000, 4097, 8191, 8192, 8193, 65536, 100003, 131071, 131072, 131073])
 def test_epoch_shuffle_matches_oracle_bit_exact(dtype, n):
     """wr_epoch_shuffle: out_k[i] = col_k[perm(i)] with perm = oracle.epoch_permutation, a bijection of [0, n) — the
     device's epoch order (reference: DataLoader(shuffle=True), BaseRunner.py:188-193)."""
@@ -100,6 +161,30 @@ def test_epoch_shuffle_matches_oracle_bit_exact(dtype, n):
     if n >= 1000:
         (o1,) = hip_ops.epoch_shuffle([torch.from_numpy(cols[0]).to(dtype).to(dev)], 3407, 6)
         assert not torch.equal(o1, o0)
+
+
+def test_epoch_shuffle_order_is_uniform():
+    """The device's own orders of 64 epochs at n = 100003 under the battery for the order: position bucket against source
+    bucket, neighbours kept together, epochs repeating each other, and batches of 2,048 rows as uniform samples of an epoch
+    whose rows are ordered (the reference's are, by user)."""
+    from whisprrec_amd import hip_ops
+    dev = torch.device("cuda:0")
+    n, K = 100003, 64
+    col = torch.arange(n, dtype=torch.int32, device=dev)
+    perms = np.empty((K, n), np.int64)
+    for e in range(K):
+        (out,), order = hip_ops.epoch_shuffle([col], 3407, e, want_order=True)
+        perms[e] = order.cpu().numpy()
+        assert torch.equal(out.long(), order)
+    assert np.array_equal(np.sort(perms, axis=1), np.broadcast_to(np.arange(n), (K, n)))
+    assert np.array_equal(perms, E.permutations(n, 3407, np.arange(K)))
+    tag = "device shuffle n=%d K=%d" % (n, K)
+    _inside(tag + " bucket_chi2 G=64", E.bucket_chi2(perms, 64))
+    for name, fn in (("successor_count", E.successor_count), ("same_as_previous", E.same_as_previous)):
+        z, mean = fn(perms)
+        _inside("%s %s" % (tag, name), z, "mean %.4f" % mean)
+    for e in range(8):
+        _inside("%s batch_composition B=2048 G=16 epoch %d" % (tag, e), E.batch_composition(perms[e], 2048, 16))
 
 
 def test_epoch_shuffle_full_size_is_a_permutation():
@@ -186,6 +271,38 @@ def test_fused_range_preparation_equals_sampler_then_shuffle(dtype):
     p2.fill(0, n)
     with pytest.raises(IndexError):
         p2.check()
+
+
+@pytest.mark.parametrize("dtype", [torch.int64, torch.int32])
+def test_fused_preparation_draws_from_the_rule(dtype):
+    """EpochPrep.fill end to end, packed source rows and the pair set, filled in two ranges: the negatives column against its
+    expectation under the rule given the SHUFFLED users column beside it (not through equality with the other two kernels),
+    on a frame ordered by user as the reference's is"""
+    from whisprrec_amd import hip_ops
+    dev = torch.device("cuda:0")
+    rng = np.random.RandomState(7)
+    nU, nI, n = 2000, 5000, 200_003
+    sets = {u: set(rng.randint(0, nI, rng.randint(1, 60)).tolist()) for u in range(nU)}
+    ptr, idx = _csr(sets, nU)
+    users = np.sort(rng.randint(0, nU, n))
+    items = idx[ptr[users] + rng.randint(0, 1 << 30, n) % (ptr[users + 1] - ptr[users])].astype(np.int64)   # a clicked item each
+    tu, ti = torch.from_numpy(users).to(dev).to(dtype), torch.from_numpy(items).to(dev).to(dtype)
+    tptr, tidx = torch.from_numpy(ptr).to(dev), torch.from_numpy(idx).to(dev)
+    prep = hip_ops.EpochPrep(tu, ti, nU, nI, None, None, 3407, 2, want_order=True, pairs=hip_ops.pair_set(tptr, tidx, nU),
+                             packed=hip_ops.pack_rows(tu, ti))
+    assert prep.packed is not None
+    for lo, hi in ((65536, n), (0, 65536)):
+        prep.fill(lo, hi)
+    torch.cuda.synchronize()
+    prep.check()
+    assert int(prep.err.item()) == 0
+    su, si, sn = (c.cpu().numpy().astype(np.int64) for c in prep.cols)
+    order = prep.order.cpu().numpy()
+    assert np.array_equal(np.sort(order), np.arange(n))
+    assert np.array_equal(su, users[order]) and np.array_equal(si, items[order])
+    assert E.forbidden(sn, su, sets, nI) == 0
+    _inside("device EpochPrep packed %s item_chi2" % str(dtype)[6:], E.item_chi2(sn, su, sets, nI))
+    _inside("device EpochPrep packed %s batch_composition B=2048 G=16" % str(dtype)[6:], E.batch_composition(order, 2048, 16))
 
 
 def test_pipelined_preparation_trains_the_same_epoch():

@@ -2,7 +2,12 @@
 // (wr_views.hip): an alternating Feistel network on ceil(log2 n) bits (the two halves take turns being XORed with a splitmix64
 // hash of the other half, the round number and the key; kShuffleRounds rounds) with cycle walking (re-apply until the value is
 // < n; the domain is < 2n for n >= 4, so < 2 evaluations on average).  Evaluated per element: no sort, no order array.
-// oracle.epoch_permutation_at restates it bit for bit.
+// oracle.epoch_permutation_at restates it bit for bit; that is the project's own generator restated, so what holds the ORDER to
+// a uniform one is the battery of tests/test_epoch_prep_contract.py (bucket tables, successors, fixed points, consecutive epochs,
+// batch composition; 2, 3 and 4 rounds fail it, 6 could not be told from 8).  Known limit: the halves are 1 to 2 bits wide below
+// n = 16 and the single-position marginals are then measurably not uniform (z = 7.2 / 4.6 / 2.6 at n = 5 / 6 / 9 over 20,000
+// epochs, cell probabilities off by up to 6 %); from n = 16 up they pass (asserted at n = 16, 17, 32, 33, 64).  An epoch of
+// fewer than 16 rows does not occur in the data this project targets.
 #pragma once
 #include "wr_common.h"
 
