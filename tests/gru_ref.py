@@ -11,7 +11,8 @@ Figures: max |a - b| / max |b| per array (0 where both are exactly zero).  Group
 Tolerances: DESIGN section 2's rule.  The floor of a group is the stock fp32 path (nn.GRU over the padded batch, the row at
 lengths - 1, under autograd: what --gru_native 0 runs) against this restatement on a CPU; FLOORS holds the largest floor over
 SHAPES x PATTERNS; TOL = 8 x that, rounded up to one digit.  tests/test_gru4rec_contract.py re-measures the floors and asserts
-4 x floor < TOL.
+4 x floor < TOL.  WALK_SHAPES (more 16-row tiles than the kernels' workgroup caps: a workgroup takes several tiles) has
+WALK_FLOORS / WALK_TOL of its own, by the same rule.
 """
 import numpy as np
 
@@ -29,6 +30,29 @@ WRONGS = ("bhn_outside", "swap_z", "late_last", "gbhh_no_n", "gwhh_tile_row", "g
 FLOORS = {"h": 3.3e-7, "gx": 3.3e-7, "gw": 6.0e-7, "gb": 5.6e-7}
 TOL = {"h": 3e-6, "gx": 3e-6, "gw": 5e-6, "gb": 5e-6}                       # 8 x floor, rounded up to one digit
 
+# The caps of wr_gru.hip restated, in rows: a workgroup takes the 16-row tiles tile, tile + cap, ... once B exceeds cap x 16 rows.
+TILE = 16                   # kGruRows
+FWD_ROWS = TILE * 1024      # kGruRows * kGruFwdWg
+BWD_ROWS = TILE * 256       # kGruRows * kGruBwdWg: the workgroups of the backward carry the parameter-gradient partials
+
+# Shapes at which a workgroup visits several tiles.  (8195, 3, 32, 32): 513 tiles on the 256 workgroups of the backward, the last
+# tile of 3 rows — every pattern; the others with "mixed" only: (4130, 20, 64, 64) and (4100, 5, 64, 32) give a few workgroups a
+# second tile (the last of 2 / 4 rows), (16400, 2, 32, 64) has 1,025 tiles: the forward walks too, the backward 4 - 5 times.
+WALK_SHAPES = [(8195, 3, 32, 32), (4130, 20, 64, 64), (4100, 5, 64, 32), (16400, 2, 32, 64)]
+WALK_SEED = 19100                             # make_case's seed base of this list (SHAPES: 9100)
+
+
+def walk_patterns(i):
+    return PATTERNS if i == 0 else ("mixed",)
+
+
+# Largest floor of each group over WALK_SHAPES x walk_patterns, measured as FLOORS is (measure_floors(walk=True))
+# — the same in repeated runs.  h and gx peak at (16400, 2, 32, 64), gw at (8195, 3, 32, 32) "full".
+WALK_FLOORS = {"h": 3.84e-7, "gx": 4.05e-7, "gw": 3.98e-7, "gb": 1.92e-7}
+WALK_TOL = {"h": 4e-6, "gx": 4e-6, "gw": 4e-6, "gb": 2e-6}                  # 8 x floor, rounded up to one digit
+# The wrong results of a walk (walk_wrong below), smallest largest-figure / WALK_TOL over the walk cases: later_visits_dropped 2.0e4,
+# later_visits_stale 2.3e5, length_of_first_visit 1.7e5 ("mixed" only: with equal lengths it is no mutant), h_carry 9.1e4.
+
 
 # ------------------------------------------------------------------------------------------------ inputs
 def make_lengths(pattern, B, T, rng):
@@ -43,11 +67,12 @@ def make_lengths(pattern, B, T, rng):
     return n
 
 
-def make_case(i, pattern):
+def make_case(i, pattern, shapes=None, seed=9100):
     """-> dict(x [B, T, E], lengths int64 [B], wih [3H, E], whh [3H, H], bih, bhh [3H], glast [B, H]) of SHAPES[i], fp32; x is
-    zero at t >= lengths[b] (left-aligned, zero-padded histories); the biases are not zero (scale 0.2)"""
-    B, T, E, H = SHAPES[i]
-    rng = np.random.RandomState(9100 + 10 * i + PATTERNS.index(pattern))
+    zero at t >= lengths[b] (left-aligned, zero-padded histories); the biases are not zero (scale 0.2).
+    shapes / seed: another list (WALK_SHAPES) with its own seed base"""
+    B, T, E, H = (SHAPES if shapes is None else shapes)[i]
+    rng = np.random.RandomState(seed + 10 * i + PATTERNS.index(pattern))
     f = lambda *s: rng.standard_normal(s)                   # noqa: E731
     c = {"x": f(B, T, E) * 0.5, "wih": f(3 * H, E) / np.sqrt(E), "whh": f(3 * H, H) / np.sqrt(H), "bih": f(3 * H) * 0.2,
          "bhh": f(3 * H) * 0.2, "glast": f(B, H)}
@@ -62,9 +87,9 @@ def _sig(a):
     return 1.0 / (1.0 + np.exp(-a))
 
 
-def gru_f64(x, lengths, wih, whh, bih, bhh, glast=None, wrong=None):
+def gru_f64(x, lengths, wih, whh, bih, bhh, glast=None, wrong=None, h0=None):
     """-> dict(h [B, H], hs [B, T, H] and, with glast, gx, gwih, gwhh, gbih, gbhh).  `wrong` builds deliberately WRONG results for
-    the power checks (WRONGS)."""
+    the power checks (WRONGS).  h0 [B, H]: a start state other than zero (walk_wrong's 'h_carry' only)."""
     f = np.float64
     x, wih, whh, bih, bhh = (np.asarray(a, f) for a in (x, wih, whh, bih, bhh))
     B, T, E = x.shape
@@ -73,7 +98,7 @@ def gru_f64(x, lengths, wih, whh, bih, bhh, glast=None, wrong=None):
     run = np.minimum(n_steps + 1, T) if wrong == "late_last" else n_steps           # steps the row takes
     live = np.arange(T)[None, :] < run[:, None]                                    # [B, T]
     x = np.where((np.arange(T)[None, :] < n_steps[:, None])[:, :, None], x, 0.0)    # the padding is never read
-    h = np.zeros((B, H), f)
+    h = np.zeros((B, H), f) if h0 is None else np.asarray(h0, f).copy()
     hs, keep = np.zeros((B, T, H), f), []
     for t in range(T):
         gi, gh = x[:, t] @ wih.T + bih, h @ whh.T + bhh
@@ -146,9 +171,55 @@ def worst(fig):
     return w
 
 
-def fmt(tag, fig):
-    w = worst(fig)
-    return "parity gru %s: " % tag + " ".join("%s %.2e (tol %.0e)" % (g, w[g], TOL[g]) for g in GROUPS)
+def fmt(tag, fig, tol=None):
+    w, tol = worst(fig), TOL if tol is None else tol
+    return "parity gru %s: " % tag + " ".join("%s %.2e (tol %.0e)" % (g, w[g], tol[g]) for g in GROUPS)
+
+
+# ------------------------------------------------------------------------------------------------ several tiles per workgroup
+PER_ROW = ("h", "gx")
+WALK_WRONGS = ("later_visits_dropped", "later_visits_stale", "length_of_first_visit", "h_carry")
+
+
+def first_visit_of(B, cap):
+    """int64 [B]: b for b < cap, b - cap after it — the row a workgroup held in the same place one visit earlier"""
+    src = np.arange(B)
+    src[cap:] -= cap
+    return src
+
+
+def visit_figures(got, ref, cap):
+    """{name: (first, later)}: the figure of h and gx apart for the rows of a workgroup's first tile (b < cap) and of its later
+    ones, both against the whole array's max |ref|"""
+    fig = {}
+    for n in PER_ROW:
+        a, b = np.asarray(got[n], np.float64), np.asarray(ref[n], np.float64)
+        den = max(float(np.max(np.abs(b))), 1e-300)
+        fig[n] = (float(np.max(np.abs(a[:cap] - b[:cap]))) / den, float(np.max(np.abs(a[cap:] - b[cap:]))) / den if len(b) > cap else 0.0)
+    return fig
+
+
+def visit_fmt(fig):
+    return " ".join("%s first %.2e later %.2e" % (n, *v) for n, v in fig.items())
+
+
+def walk_wrong(c, ref, wrong, cap):
+    """deliberately WRONG results of a walk over `cap` rows per visit: 'later_visits_dropped' (the four parameter gradients summed
+    over the rows b < cap only), 'later_visits_stale' (h and gx of row b >= cap those of row b - cap), 'length_of_first_visit'
+    (row b >= cap takes the steps of row b - cap), 'h_carry' (row b >= cap starts from the final state of row b - cap, not zero)"""
+    B = len(c["lengths"])
+    src = first_visit_of(B, cap)
+    if wrong == "later_visits_dropped":
+        part = gru_f64(c["x"][:cap], c["lengths"][:cap], c["wih"], c["whh"], c["bih"], c["bhh"], c["glast"][:cap])
+        return dict(ref, **{n: part[n] for n in ("gwih", "gwhh", "gbih", "gbhh")})
+    if wrong == "later_visits_stale":
+        return dict(ref, **{n: ref[n][src] for n in PER_ROW})
+    if wrong == "length_of_first_visit":
+        return case_f64(dict(c, lengths=c["lengths"][src]))
+    if wrong == "h_carry":
+        h0 = np.where((np.arange(B) >= cap)[:, None], ref["h"][src], 0.0)
+        return gru_f64(c["x"], c["lengths"], c["wih"], c["whh"], c["bih"], c["bhh"], c["glast"], h0=h0)
+    raise ValueError(wrong)
 
 
 # ------------------------------------------------------------------------------------------------ the stock path
@@ -186,12 +257,14 @@ def stock(c, dtype=None, device="cpu", packed=False):
             "gbhh": rnn.bias_hh_l0.grad.cpu().numpy()}
 
 
-def measure_floors(shapes=None, patterns=PATTERNS):
-    """-> {group: largest figure of the stock fp32 path against float64 on a CPU}, and the per-case figures"""
+def measure_floors(shapes=None, patterns=PATTERNS, walk=False):
+    """-> {group: largest figure of the stock fp32 path against float64 on a CPU}, and the per-case figures; `shapes`: indices
+    into SHAPES, or into WALK_SHAPES with walk=True (patterns: those of walk_patterns, unless given)"""
     floors, cases = {g: 0.0 for g in GROUPS}, {}
-    for i in (range(len(SHAPES)) if shapes is None else shapes):
-        for pat in patterns:
-            c = make_case(i, pat)
+    lst = (WALK_SHAPES, WALK_SEED) if walk else (None, 9100)
+    for i in (range(len(WALK_SHAPES if walk else SHAPES)) if shapes is None else shapes):
+        for pat in (walk_patterns(i) if walk and patterns is PATTERNS else patterns):
+            c = make_case(i, pat, *lst)
             w = worst(figures(stock(c), case_f64(c)))
             cases[(i, pat)] = w
             for g in GROUPS:

@@ -6,7 +6,8 @@ reference formula under autograd, tests/test_hip_if4rec.py checks the kernels ag
 Tolerances (DESIGN.md section 2's rule).  FLOORS[k] is the largest figure k of the STOCK fp32 torch path — the reference's own
 operations, global-maximum shift included — against float64 on a CPU over CASES (all-zero rows left out: autograd gives them
 NaN); TOL = 8 x the largest floor, rounded up to one digit.  tests/test_if4rec_contract.py re-measures the floors and asserts
-4 x floor < TOL.
+4 x floor < TOL.  WALK_CASES (B above the kernels' workgroup caps: a workgroup visits several sequences) has WALK_FLOORS /
+WALK_TOL of its own, by the same rule.
 """
 import numpy as np
 
@@ -24,6 +25,23 @@ FIGURES = ("out", "g_hp", "g_item", "g_pos", "gW1", "gb1", "gW2", "gb2")
 FLOORS = {"out": 7.40e-7, "g_hp": 9.33e-7, "g_item": 5.78e-7, "g_pos": 4.58e-7, "gW1": 9.94e-7, "gb1": 4.23e-7, "gW2": 5.46e-7,
           "gb2": 2.44e-7}
 TOL = 8e-6             # 8 x 9.94e-7 = 7.95e-6, rounded up to one digit
+
+# The caps of wr_if4rec.hip restated: a workgroup takes the sequences b, b + cap, b + 2 cap, ... once B exceeds the cap.
+FWD_WG = 4096          # kIpFwdWg: workgroups of the forward
+BWD_WG = 512           # kIpBwdWg: workgroups of the backward, which carry the partials of gW1, gb1, gW2, gb2 and g_pos across visits
+
+# Cases at which a workgroup visits several sequences (backward: 2 - 3 visits, the last one ragged; (4099, 2, 64, 8, 1) walks the
+# forward too and gives the backward 8 - 9 visits).  make_case's row kinds, and among the later visits a row of length 1 (row
+# BWD_WG + 1) and all-zero rows (the last row and, where that is another one, row BWD_WG + 2).
+WALK_CASES = [(1027, 5, 32, 8, 2), (4099, 2, 64, 8, 1), (1030, 3, 128, 16, 3), (515, 20, 64, 8, 4)]
+WALK_SEED = 11400      # make_case's seed base of this list (CASES: 1400)
+# measured by tests/test_if4rec_contract.py::test_walk_floors_and_tolerance, as FLOORS is
+# (one thread; all-zero rows left out).  g_pos and gW2 peak at (4099, 2, 64, 8, 1): sums over 4,099 sequences of K = 1, T = 2.
+WALK_FLOORS = {"out": 1.89e-7, "g_hp": 2.16e-7, "g_item": 3.72e-7, "g_pos": 1.80e-6, "gW1": 4.21e-7, "gb1": 2.37e-7, "gW2": 1.67e-6,
+               "gb2": 3.03e-7}
+WALK_TOL = 2e-5        # 8 x 1.80e-6 = 1.44e-5, rounded up to one digit
+# The wrong results of a walk (walk_wrong below), smallest largest-figure / WALK_TOL over WALK_CASES: later_visits_dropped 7.8e3,
+# later_visits_stale 3.8e4, length_of_first_visit 4.9e4.
 
 
 # The model on the reference's batch (g14): the loss and every gradient are held to TOL, except the gradients that arrive through
@@ -52,11 +70,13 @@ def model_tol(name):
     return MODEL_QK_TOL if name.endswith(SCORE_PATH) else TOL
 
 
-def make_case(i):
+def make_case(i, cases=None, seed=1400):
     """inputs of case i as float32 / int64 arrays.  Every case with B >= 3 holds a row of length 1 (row 0), a full row (row 1),
-    an all-zero row (the last) and, when B >= 4 and T >= 3, a row with an interior zero (row 2)."""
-    B, T, D, A, K = CASES[i]
-    rng = np.random.RandomState(1400 + i)
+    an all-zero row (the last) and, when B >= 4 and T >= 3, a row with an interior zero (row 2).
+    cases / seed: another list (WALK_CASES) with its own seed base; its cases also hold a row of length 1 and an all-zero row
+    among the sequences a workgroup of the backward meets on a later visit."""
+    B, T, D, A, K = (CASES if cases is None else cases)[i]
+    rng = np.random.RandomState(seed + i)
     item = (rng.standard_normal((N_ITEMS, D)) * 0.5).astype(np.float32)
     pos = (rng.standard_normal((T + 1, D)) * 0.5).astype(np.float32)
     W1 = (rng.standard_normal((A, D)) / np.sqrt(D)).astype(np.float32)
@@ -75,7 +95,12 @@ def make_case(i):
         hist[2, 1] = 0
     if B >= 3:
         hist[B - 1] = 0
-    if i == SPREAD_CASE:
+    if cases is not None:
+        lengths[BWD_WG + 1] = 1
+        hist[BWD_WG + 1, 1:] = 0
+        if BWD_WG + 2 < B - 1:
+            hist[BWD_WG + 2] = 0
+    if i == SPREAD_CASE and cases is None:
         c = dict(item=item, pos=pos, hist=hist, W1=W1, b1=b1, W2=W2, b2=b2)
         s = pool_ref(c)["s"]
         W2 = (W2 * (60.0 / np.abs(s[np.isfinite(s)]).max())).astype(np.float32)
@@ -93,14 +118,14 @@ def drop_zero_rows(c):
     return out
 
 
-def pool_ref(c, variant=None, g_out=None):
+def pool_ref(c, variant=None, g_out=None, valid=None):
     """float64 pooling of case dict c and, with g_out, every gradient.  variant: one of WRONG_POOL (a deliberately wrong
-    formula), or None."""
+    formula), or None.  valid: bool [B, T], a history mask other than hist > 0 (walk_wrong's 'length_of_first_visit' only)."""
     f = np.float64
     item, pos, W1, b1, W2, b2 = (c[k].astype(f) for k in ("item", "pos", "W1", "b1", "W2", "b2"))
     hist = c["hist"]
     B, T = hist.shape
-    valid = hist > 0
+    valid = hist > 0 if valid is None else np.asarray(valid, bool)
     if variant == "mask_by_lengths":
         valid = np.arange(T)[None, :] < c["lengths"][:, None]
     pidx = np.arange(T)[None, :] * valid
@@ -138,6 +163,49 @@ def pool_ref(c, variant=None, g_out=None):
 
 
 WRONG_POOL = ("mask_by_lengths", "relu", "softmax_over_k", "no_position", "zero_row_nan")
+
+
+# ------------------------------------------------------------------------------------------------ several visits per workgroup
+PER_SEQUENCE = ("out", "g_hp")
+WALK_WRONG = ("later_visits_dropped", "later_visits_stale", "length_of_first_visit")
+
+
+def first_visit_of(B, cap):
+    """int64 [B]: b for b < cap, b - cap after it — the sequence a workgroup saw one visit earlier"""
+    src = np.arange(B)
+    src[cap:] -= cap
+    return src
+
+
+def visit_figures(got, ref, cap):
+    """{name: (first, later)}: the figure of out and g_hp apart for the sequences of a workgroup's first visit (b < cap) and of
+    its later ones, both against the whole array's max |ref|"""
+    fig = {}
+    for n in PER_SEQUENCE:
+        a, b = np.asarray(got[n], np.float64), np.asarray(ref[n], np.float64)
+        den = max(float(np.abs(b).max()), 1e-300)
+        fig[n] = (float(np.abs(a[:cap] - b[:cap]).max()) / den, float(np.abs(a[cap:] - b[cap:]).max()) / den if len(b) > cap else 0.0)
+    return fig
+
+
+def visit_fmt(fig):
+    return " ".join("%s first %.2e later %.2e" % (n, *v) for n, v in fig.items())
+
+
+def walk_wrong(c, ref, wrong, cap):
+    """deliberately WRONG results of a walk: 'later_visits_dropped' (gW1, gb1, gW2, gb2 and g_pos summed over the sequences
+    b < cap only), 'later_visits_stale' (out and g_hp of sequence b >= cap those of b - cap), 'length_of_first_visit' (sequence
+    b >= cap under the history mask of b - cap)"""
+    src = first_visit_of(c["hist"].shape[0], cap)
+    if wrong == "later_visits_dropped":
+        cut = dict(c, hist=c["hist"][:cap], lengths=c["lengths"][:cap])
+        part = pool_ref(cut, g_out=c["g_out"][:cap])
+        return dict(ref, **{k: part[k] for k in ("gW1", "gb1", "gW2", "gb2", "g_pos")})
+    if wrong == "later_visits_stale":
+        return dict(ref, **{k: ref[k][src] for k in PER_SEQUENCE})
+    if wrong == "length_of_first_visit":
+        return pool_ref(c, g_out=c["g_out"], valid=(c["hist"] > 0)[src])
+    raise ValueError(wrong)
 
 
 def figure(x, ref, scale=None):

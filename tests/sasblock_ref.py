@@ -15,6 +15,10 @@ mathematically zero (q . b_k is constant along a softmax row): it is measured ab
 Tolerances: DESIGN section 2's rule.  The floor of a figure is the stock fp32 `_Block` (torch.autograd) against this
 restatement on a CPU; FLOORS holds the largest floor over SHAPES at p = 0 and at p = 0.1 (explicit mask); TOL = 8 x that,
 rounded up to one digit.  tests/test_sasblock_contract.py re-measures the floors and asserts 4 x floor < TOL.
+
+WALK_SHAPES (a workgroup visits several sequences: B above the kernels' workgroup caps) and FORM_SHAPES (every <D, TM> form of the
+kernels at its border) have floors and tolerances of their own, by the same rule, and the same test re-measures them; the deliberately
+WRONG results of a walk (`later_visits_dropped`, stale(), a mask or a maximum taken at the first visit) stand 5 x WALK_TOL out.
 """
 import numpy as np
 
@@ -32,6 +36,39 @@ SHAPES = [(96, 20, 64, 4), (3, 1, 64, 4), (5, 7, 32, 2), (2, 33, 64, 2), (130, 6
 # The largest ones come from (37, 20, 32, 4): d_k = 8, and the q / k gradients are sums of cancelling softmax terms.
 FLOORS = {"out": 3.3e-7, "gx": 3.4e-7, "gqk": 5.2e-6, "gparam": 1.3e-6, "gkb": 9.6e-6}
 TOL = {"out": 3e-6, "gx": 3e-6, "gqk": 5e-5, "gparam": 2e-5, "gkb": 8e-5}          # 8 x floor, rounded up to one digit
+
+# The caps of wr_sasblock.hip restated: a workgroup takes the sequences b, b + cap, b + 2 cap, ... once B exceeds the cap.
+FWD_WG = 2048      # kSasFwdWg: workgroups of forward launch 1, the partial maxima (launch 2 runs one workgroup per sequence)
+BWD_WG = 512       # kSasBwdWg: workgroups of the backward, which carry the parameter-gradient partials across their visits
+
+# Shapes at which a workgroup visits several sequences: most workgroups of the backward visit two, a few three, the last
+# visit is ragged; (2051, 2, 64, 4) also walks forward launch 1 (2,048 + 3) and gives the backward 4 - 5 visits;
+# (515, 20, 64, 4) is the production form; (515, 33, 32, 2) is the <32, 64> form, which walks as well.  Each runs at p = 0
+# and p = 0.1: the mask index is (b T + t) D + d, so dropout parity on a later visit checks the true b.
+WALK_SHAPES = [(1027, 5, 32, 2), (2051, 2, 64, 4), (515, 20, 64, 4), (515, 33, 32, 2)]
+# The <D, TM> forms of WR_SAS_DISPATCH ({32, 64} x {24, 64}) at their border: T = 24 fills a TM = 24 tile, T = 25 is the first
+# T of the TM = 64 form; (4, 64, 32, 1) fills the <32, 64> tile.
+FORM_SHAPES = [(3, 25, 32, 4), (4, 64, 32, 1), (3, 24, 64, 2), (3, 24, 32, 2), (3, 25, 64, 2)]
+WALK_SEED, FORM_SEED = 17000, 27000           # make_case's seed bases of the two lists (SHAPES: 7000)
+
+# Largest floor of each figure over the list x {p = 0, p = 0.1}, measured as FLOORS is (test_sasblock_contract.py prints them).
+# WALK: gqk and gkb peak at (2051, 2, 64, 4) p = 0 (T = 2: the score gradients are differences of two nearly equal terms), gparam
+# at (515, 33, 32, 2) p = 0.1.  FORM: gqk at (3, 25, 32, 4) p = 0.1, gkb at (3, 24, 64, 2) p = 0.
+WALK_FLOORS = {"out": 2.74e-7, "gx": 3.16e-7, "gqk": 4.27e-6, "gparam": 1.63e-6, "gkb": 1.50e-5}
+FORM_FLOORS = {"out": 2.69e-7, "gx": 2.70e-7, "gqk": 2.12e-6, "gparam": 5.48e-7, "gkb": 9.08e-6}
+# 8 x floor, rounded up to one digit (rule_of below); TOL's own value where the rule lands on it
+WALK_TOL = {"out": TOL["out"], "gx": TOL["gx"], "gqk": 4e-5, "gparam": TOL["gparam"], "gkb": 2e-4}
+FORM_TOL = {"out": TOL["out"], "gx": TOL["gx"], "gqk": 2e-5, "gparam": 5e-6, "gkb": TOL["gkb"]}
+# The wrong results of a walk (tests/test_sasblock_contract.py), smallest largest-figure / WALK_TOL over WALK_SHAPES at p = 0.1:
+# later_visits_dropped 4.6e3 (at (515, 20, 64, 4): 3 of 515 sequences missing), later_visits_stale 2.9e5, mask_of_first_visit 1.8e5;
+# max_of_first_visit misses the stored maximum (21.92 at x[2049] x 100) by 21.91, against the 1e-5 relative it is held to.
+
+
+def rule_of(floor):
+    """DESIGN section 2's rule: 8 x floor, rounded up to one digit"""
+    v = 8.0 * floor
+    e = int(np.floor(np.log10(v)))
+    return float("%de%d" % (int(np.ceil(v / 10.0 ** e - 1e-9)), e))
 
 
 # ------------------------------------------------------------------------------------------------ dropout mask
@@ -91,11 +128,12 @@ def xavier_params(D, heads, rng):
     return sd
 
 
-def make_case(i, g5=None):
-    """-> (x [B, T, D] fp32, params, upstream gradient [B, T, D] fp32, heads) of SHAPES[i]; case 0 needs the g5 set"""
-    B, T, D, heads = SHAPES[i]
-    rng = np.random.RandomState(7000 + i)
-    if i == 0:
+def make_case(i, g5=None, shapes=None, seed=7000):
+    """-> (x [B, T, D] fp32, params, upstream gradient [B, T, D] fp32, heads) of SHAPES[i]; case 0 needs the g5 set.
+    shapes / seed: another list (WALK_SHAPES, FORM_SHAPES) with its own seed base; SHAPES' data does not depend on them."""
+    B, T, D, heads = (SHAPES if shapes is None else shapes)[i]
+    rng = np.random.RandomState(seed + i)
+    if i == 0 and shapes is None:
         pre = "sd__transformer_block.0."
         sd = {n: np.asarray(g5[pre + n], np.float32) for n in PARAMS}
         x = (g5["sd__item_embedding.weight"][g5["hist"]] + g5["sd__position_embedding.weight"][np.arange(T)][None]).astype(np.float32)
@@ -104,7 +142,7 @@ def make_case(i, g5=None):
         # the scale of xavier-initialised tables (3,706 items): item + position rows
         x = (rng.standard_normal((B, T, D)) * np.sqrt(2.0 / (3706 + D)) * np.sqrt(2.0)).astype(np.float32)
     # parameters away from their initial 0 / 1 so that every gradient path carries weight
-    rp = np.random.RandomState(7100 + i)
+    rp = np.random.RandomState(seed + 100 + i)
     for n in PARAMS:
         if n.endswith("bias"):
             sd[n] = (sd[n] + 0.05 * rp.standard_normal(sd[n].shape)).astype(np.float32)
@@ -128,13 +166,14 @@ def _ln_bwd(dy, xh, rstd, g):
     return rstd * (dxh - dxh.mean(-1, keepdims=True) - xh * (dxh * xh).mean(-1, keepdims=True))
 
 
-def block_f64(x, sd, heads, gout=None, m1=None, m2=None, wrong=None, zero_below=None, zero_rows=None):
+def block_f64(x, sd, heads, gout=None, m1=None, m2=None, wrong=None, zero_below=None, zero_rows=None, first=None):
     """-> dict(out, gmax, P [B, h, T, T], zero_rows [B, h, T] and, with gout, gx and g[name] for every parameter).
     m1 / m2: multiplicative dropout masks (keep * scale) or None.  `wrong` builds deliberately WRONG blocks for the power
     checks: 'no_scale', 'mask_shift', 'ln_no_eps', 'ln_no_bias_grad', 'drop_no_scale:<scale>', 'v_head', 'relu_gate',
     'skip_seq'.  zero_below: a score row whose own maximum lies more than this far below the call's maximum is zeroed, as
     it is in any fp32 evaluation (exp underflows to 0 at -104, at -88 without denormals; float64 only at -745).
-    zero_rows: bool [B, h, T], score rows to zero on top of that."""
+    zero_rows: bool [B, h, T], score rows to zero on top of that.
+    first: with wrong = 'later_visits_dropped', the number of sequences whose terms enter the parameter-gradient sums."""
     f = np.float64
     x = np.asarray(x, f)
     W = {n: np.asarray(sd[n], f) for n in PARAMS}
@@ -179,7 +218,7 @@ def block_f64(x, sd, heads, gout=None, m1=None, m2=None, wrong=None, zero_below=
     H = np.maximum(pre, 0.0)
     O2 = H @ W["linear2.weight"].T + W["linear2.bias"]
     out, xh2, rstd2 = _ln_fwd(O2 * m2 + C, W["layer_norm2.weight"], W["layer_norm2.bias"], eps)
-    res = {"out": out, "gmax": float(gmax), "P": P, "zero_rows": zero[..., 0], "A": A, "gap": gap}
+    res = {"out": out, "gmax": float(gmax), "P": P, "zero_rows": zero[..., 0], "A": A, "gap": gap, "seq_max": S.max((1, 2, 3))}
     if gout is None:
         return res
     G = np.asarray(gout, f)
@@ -187,6 +226,8 @@ def block_f64(x, sd, heads, gout=None, m1=None, m2=None, wrong=None, zero_below=
     keep = np.ones(B, bool)
     if wrong == "skip_seq":
         keep[B - 1] = False                      # one sequence missing from every weight-gradient sum
+    if wrong == "later_visits_dropped":
+        keep[first:] = False                     # only each workgroup's first visit reaches the weight-gradient sums
 
     def wsum(a, b):                              # sum over sequences and positions of a^T b
         return np.einsum("btj,btd->jd", a[keep], b[keep])
@@ -261,9 +302,40 @@ def worst(fig):
     return w
 
 
-def fmt(tag, fig):
-    w = worst(fig)
-    return "parity sasblock %s: " % tag + " ".join("%s %.2e (tol %.0e)" % (k, w[k], TOL[k]) for k in GROUPS)
+def fmt(tag, fig, tol=None):
+    w, tol = worst(fig), TOL if tol is None else tol
+    return "parity sasblock %s: " % tag + " ".join("%s %.2e (tol %.0e)" % (k, w[k], tol[k]) for k in GROUPS)
+
+
+# ------------------------------------------------------------------------------------------------ several visits per workgroup
+def first_visit_of(B, cap):
+    """int64 [B]: b for b < cap, b - cap after it — the sequence a workgroup saw one visit earlier"""
+    src = np.arange(B)
+    src[cap:] -= cap
+    return src
+
+
+def visit_figures(got, ref, cap, names=("out", "gx")):
+    """{name: (first, later)}: the figure of each per-sequence array apart for the sequences of a workgroup's first visit
+    (b < cap) and of its later ones, both against the whole array's max |ref| — the larger of the two is figures()'s"""
+    fig = {}
+    for n in names:
+        a, b = np.asarray(got[n], np.float64), np.asarray(ref[n], np.float64)
+        den = max(float(np.max(np.abs(b))), 1e-300)
+        fig[n] = (float(np.max(np.abs(a[:cap] - b[:cap]))) / den, float(np.max(np.abs(a[cap:] - b[cap:]))) / den if len(b) > cap else 0.0)
+    return fig
+
+
+def visit_fmt(fig):
+    return " ".join("%s first %.2e later %.2e" % (n, *v) for n, v in fig.items())
+
+
+def stale(res, cap, names=("out", "gx")):
+    """the WRONG result `later_visits_stale`: what belongs to sequence b >= cap replaced by that of sequence b - cap"""
+    bad = dict(res)
+    for n in names:
+        bad[n] = np.asarray(res[n])[first_visit_of(len(res[n]), cap)]
+    return bad
 
 
 def stock_fp32(x, sd, heads, gout, m1=None, m2=None, device="cpu", dtype=None):

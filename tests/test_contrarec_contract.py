@@ -120,6 +120,101 @@ def test_wrong_masks_land_above_the_tolerances(block_cases, wrong):
     assert caught, wrong
 
 
+# ------------------------------------------------------------------------------------------------ several visits, every form
+SEED = 0x5A5B10C
+LISTS = {"walk": (C.BLOCK_WALK_SHAPES, C.BLOCK_WALK_SEED, C.BLOCK_WALK_FLOORS, C.BLOCK_WALK_TOL),
+         "form": (C.BLOCK_FORM_SHAPES, C.BLOCK_FORM_SEED, C.BLOCK_FORM_FLOORS, C.BLOCK_FORM_TOL)}
+_LIST_REFS = {}
+
+
+def _list_ref(which, i, p):
+    """(inputs, masks, float64 result) of a case of BLOCK_WALK_SHAPES / BLOCK_FORM_SHAPES, computed once"""
+    if (which, i, p) not in _LIST_REFS:
+        shapes, seed = LISTS[which][:2]
+        x, sd, g, heads, lens = C.make_block_case(i, shapes=shapes, seed=seed)
+        m1, m2 = R.masks_for(SEED + seed + i, *x.shape, p)
+        _LIST_REFS[(which, i, p)] = ((x, sd, g, heads, lens), (m1, m2), C.block_keys_f64(x, sd, heads, lens, g, m1=m1, m2=m2))
+    return _LIST_REFS[(which, i, p)]
+
+
+def test_block_walk_lengths_and_the_old_cases(block_cases):
+    """the keyed lists are sasblock_ref's (tests/test_sasblock_contract.py checks that they walk); every case forces the lengths 1
+    and T; the lengths met on a later visit are independent of those of the visit before; BLOCK_SHAPES' data is what it was"""
+    assert C.BLOCK_WALK_SHAPES is R.WALK_SHAPES and C.BLOCK_FORM_SHAPES is R.FORM_SHAPES
+    G = R.BWD_WG
+    for which in ("walk", "form"):
+        for i, (B, T, _, _) in enumerate(LISTS[which][0]):
+            lens = _list_ref(which, i, 0.0)[0][4]
+            assert lens.min() == 1 and lens.max() == T and lens.shape == (B,)
+            if which == "walk":
+                assert B > G and (lens[G:] != lens[:B - G]).any()
+                if T >= 5 and B - G >= 500:     # enough pairs to tell: equal by chance in 1 of T, not in all
+                    assert (lens[G:] == lens[:B - G]).mean() < 2.0 / T + 0.1
+    x, sd, g, heads, lens = block_cases[2]
+    rng = np.random.RandomState(7302)
+    R.xavier_params(32, 2, rng)
+    assert np.array_equal(x, (rng.standard_normal((5, 7, 32)) * np.sqrt(2.0 / (3706 + 32)) * np.sqrt(2.0)).astype(np.float32))
+    assert np.array_equal(lens, C.make_lengths(5, 7, rng))
+
+
+@pytest.mark.parametrize("which", ["walk", "form"])
+def test_block_walk_and_form_tolerances_stand_above_the_fp32_floor(which):
+    shapes, seed, floors, tol = LISTS[which]
+    worst = {k: 0.0 for k in tol}
+    for i in range(len(shapes)):
+        for p in (0.0, 0.1):
+            (x, sd, g, heads, lens), (m1, m2), ref = _list_ref(which, i, p)
+            fig = C.figures(*C.stock_block_fp32(x, sd, heads, g, lens, m1=m1, m2=m2), ref)
+            print(C.block_fmt("%s floor B=%d T=%d D=%d h=%d p=%g" % (which, *shapes[i], p), fig, tol))
+            for k, v in C.worst(fig).items():
+                worst[k] = max(worst[k], v)
+            if p == 0.1:                      # the restatement with its masks, in float64 under autograd
+                f64 = C.figures(*C.stock_block_fp32(x, sd, heads, g, lens, dtype=torch.float64, m1=m1, m2=m2), ref)
+                assert max(f64.values()) <= 1e-12, f64
+    print("%s floor (largest): " % which + " ".join("%s %.2e" % kv for kv in worst.items()))
+    for k in tol:
+        assert 4.0 * worst[k] < tol[k], (k, worst[k], tol[k])
+        assert 8.0 * floors[k] <= tol[k] <= 16.0 * floors[k] and tol[k] == R.rule_of(floors[k])
+        assert R.rule_of(C.BLOCK_FLOORS[k]) == C.BLOCK_TOL[k]
+
+
+BLOCK_WALK_WRONG = ["later_visits_dropped", "later_visits_stale", "mask_of_first_visit", "length_of_first_visit"]
+
+
+@pytest.mark.parametrize("wrong", BLOCK_WALK_WRONG)
+@pytest.mark.parametrize("i", range(len(C.BLOCK_WALK_SHAPES)))
+def test_block_walk_mutants_land_five_tolerances_out(i, wrong):
+    """parameter gradients of the first visits only; a later visit's output and gx those of the visit before; its dropout mask, or
+    its key length, that of the visit before — each exceeds 5 x BLOCK_WALK_TOL on some figure, at every walk shape"""
+    (x, sd, g, heads, lens), (m1, m2), ref = _list_ref("walk", i, 0.1)
+    src = R.first_visit_of(x.shape[0], R.BWD_WG)
+    if wrong == "later_visits_dropped":
+        bad = C.block_keys_f64(x, sd, heads, lens, g, wrong=wrong, m1=m1, m2=m2, first=R.BWD_WG)
+    elif wrong == "later_visits_stale":
+        bad = R.stale(ref, R.BWD_WG)
+    elif wrong == "mask_of_first_visit":
+        bad = C.block_keys_f64(x, sd, heads, lens, g, m1=m1[src], m2=m2[src])
+    else:
+        bad = C.block_keys_f64(x, sd, heads, lens[src], g, m1=m1, m2=m2)
+    fig = C.figures(bad["out"], bad["gx"], bad["g"], ref)
+    margin = {n: v / C.BLOCK_WALK_TOL[C.group_of(n)] for n, v in fig.items()}
+    print("walk mutant %s at %s: largest figure / tolerance %.1f (%s)" % (wrong, C.BLOCK_WALK_SHAPES[i], max(margin.values()),
+                                                                           max(margin, key=margin.get)))
+    assert max(margin.values()) >= 5.0, margin
+
+
+def test_block_walk_maximum_of_the_first_visits_only_misses_the_stored_maximum():
+    """`max_of_first_visit` on the GPU test's case: x of sequence 2049 of (2051, 2, 64, 4) times 100"""
+    i = C.BLOCK_WALK_SHAPES.index((2051, 2, 64, 4))
+    x, sd, g, heads, lens = C.make_block_case(i, shapes=C.BLOCK_WALK_SHAPES, seed=C.BLOCK_WALK_SEED)
+    x = x.copy()
+    x[2049] *= 100.0
+    ref = C.block_keys_f64(x, sd, heads, lens)
+    bad = ref["seq_max"][:R.FWD_WG].max()
+    assert ref["gmax"] == ref["seq_max"].max() and 10.0 < ref["gmax"] - bad < 30.0
+    assert abs(bad - ref["gmax"]) > 5.0 * 1e-5 * abs(ref["gmax"])
+
+
 @pytest.mark.parametrize("wrong", C.LOSS_WRONG)
 def test_wrong_losses_land_above_the_tolerances(loss_cases, wrong):
     """each variant exceeds 4 x TOL on a listed shape; the single shift and the missing 1e-10 on a tau = 0.05 one"""

@@ -79,6 +79,74 @@ def test_floors_hold(shape, pattern):
         assert 4 * floors[g] < R.TOL[g], (g, floors[g])
 
 
+# ------------------------------------------------------------------------------------------------ several tiles per workgroup
+WALK = [(i, pat) for i in range(len(R.WALK_SHAPES)) for pat in R.walk_patterns(i)]
+WALK_IDS = ["%s-%s" % ("x".join(map(str, R.WALK_SHAPES[i])), pat) for i, pat in WALK]
+_WALK = {}
+
+
+def _walk(i, pattern):
+    if (i, pattern) not in _WALK:
+        c = R.make_case(i, pattern, R.WALK_SHAPES, R.WALK_SEED)
+        _WALK[(i, pattern)] = (c, R.case_f64(c))
+    return _WALK[(i, pattern)]
+
+
+def _kernel_constant(name):
+    import re
+    import whisprrec_amd
+    with open(os.path.join(os.path.dirname(os.path.abspath(whisprrec_amd.__file__)), "csrc", "wr_gru.hip")) as fh:
+        return int(re.search(r"constexpr int %s = (\d+);" % name, fh.read()).group(1))
+
+
+def test_walk_shapes_walk_and_leave_the_old_cases_alone():
+    assert R.TILE == _kernel_constant("kGruRows")
+    assert R.FWD_ROWS == R.TILE * _kernel_constant("kGruFwdWg") and R.BWD_ROWS == R.TILE * _kernel_constant("kGruBwdWg")
+    assert all(B > R.BWD_ROWS for B, *_ in R.WALK_SHAPES) and sum(B % R.TILE != 0 for B, *_ in R.WALK_SHAPES) >= 3   # ragged last tiles
+    assert any(B > 2 * R.BWD_ROWS for B, *_ in R.WALK_SHAPES) and any(B > R.FWD_ROWS for B, *_ in R.WALK_SHAPES)
+    assert {(E, H) for _, _, E, H in R.WALK_SHAPES} == {(32, 32), (64, 64), (64, 32), (32, 64)}
+    assert all(B <= 130 for B, *_ in R.SHAPES)
+    c = R.make_case(1, "mixed")                                              # the draws of an old case, as before
+    rng = np.random.RandomState(9112)
+    assert np.array_equal(c["x"][1], (rng.standard_normal((5, 3, 32)) * 0.5).astype(np.float32)[1]) and c["lengths"][1] == 3
+    for i, pat in WALK:                                                      # "mixed": a later tile's lengths are its own
+        n = _walk(i, pat)[0]["lengths"]
+        if pat == "mixed":
+            assert n.min() == 1 and n.max() == R.WALK_SHAPES[i][1] and (n[R.BWD_ROWS:] != n[:len(n) - R.BWD_ROWS]).any()
+
+
+def test_walk_tolerances_are_eight_floors():
+    from sasblock_ref import rule_of
+    for g in R.GROUPS:
+        assert 8 * R.WALK_FLOORS[g] <= R.WALK_TOL[g] <= 16 * R.WALK_FLOORS[g] and R.WALK_TOL[g] == rule_of(R.WALK_FLOORS[g]), g
+
+
+@pytest.mark.parametrize("shape,pattern", WALK, ids=WALK_IDS)
+def test_walk_floors_hold(shape, pattern):
+    c, ref = _walk(shape, pattern)
+    floors = R.worst(R.figures(R.stock(c), ref))
+    print("walk floor %s %s: " % (R.WALK_SHAPES[shape], pattern) + " ".join("%s %.2e" % (g, floors[g]) for g in R.GROUPS))
+    for g in R.GROUPS:
+        assert 4 * floors[g] < R.WALK_TOL[g], (g, floors[g])
+
+
+@pytest.mark.parametrize("wrong", R.WALK_WRONGS)
+@pytest.mark.parametrize("shape,pattern", WALK, ids=WALK_IDS)
+def test_walk_mutants_land_five_tolerances_out(shape, pattern, wrong):
+    """parameter gradients of the first tiles only; a later tile's h and gx, or its lengths, those of the tile before; a later
+    tile started from the tile before's final state.  With every length equal ("ones", "full") the lengths of the tile before
+    are the right ones: that mutant is no mutant there."""
+    c, ref = _walk(shape, pattern)
+    if wrong == "length_of_first_visit" and pattern != "mixed":
+        assert np.array_equal(R.walk_wrong(c, ref, wrong, R.BWD_ROWS)["h"], ref["h"])
+        return
+    fig = R.figures(R.walk_wrong(c, ref, wrong, R.BWD_ROWS), ref)
+    margin = {n: v / R.WALK_TOL[R.GROUP_OF[n]] for n, v in fig.items()}
+    print("walk mutant %s at %s %s: largest figure / tolerance %.1f (%s)" % (wrong, R.WALK_SHAPES[shape], pattern, max(margin.values()),
+                                                                              max(margin, key=margin.get)))
+    assert max(margin.values()) >= 5.0, margin
+
+
 # ------------------------------------------------------------------------------------------------ the interface
 def _argv(path, tmp, extra=()):
     return ["--emb_size", "32", "--hidden_size", "64", "--history_max", "20", "--model_name", "GRU4Rec", "--runner_name",

@@ -36,13 +36,16 @@ def _block(sd, D, heads):
     return blk.to(DEV)
 
 
-def _run_block(x, sd, g, heads, lens, err=None):
+def _run_block(x, sd, g, heads, lens, err=None, p=0.0, seed=0, stored_max=None):
+    """stored_max: a list that receives the call's stored score maximum"""
     from whisprrec_amd import hip_ops
     blk = _block(sd, x.shape[2], heads)
     xt = _t(x).requires_grad_(True)
-    out = hip_ops.sasrec_block(xt, blk, heads, 0.0, 0, True, key_lengths=_t(lens, torch.int64), err_word=err)
+    out = hip_ops.sasrec_block(xt, blk, heads, p, seed, True, key_lengths=_t(lens, torch.int64), err_word=err)
+    if stored_max is not None:
+        stored_max.append(float(out.grad_fn.saved_tensors[1].item()))
     out.backward(_t(g))
-    return out.detach(), xt.grad.detach(), {n: p.grad.detach() for n, p in blk.named_parameters()}
+    return out.detach(), xt.grad.detach(), {n: q.grad.detach() for n, q in blk.named_parameters()}
 
 
 # ------------------------------------------------------------------------------------------------ the block with key_len
@@ -78,6 +81,99 @@ def test_block_clamps_lengths_outside_the_range_and_reports_them(g12):
     good[0], good[1] = T, 1
     out2, gx2, gp2 = _run_block(x, sd, g, heads, good)
     assert torch.equal(out, out2) and torch.equal(gx, gx2) and all(torch.equal(gp[n], gp2[n]) for n in gp)
+
+
+# ------------------------------------------------------------------------------------------------ several visits per workgroup
+SEED = 0x5A5B10C
+LISTS = {"walk": (C.BLOCK_WALK_SHAPES, C.BLOCK_WALK_SEED, C.BLOCK_WALK_TOL), "form": (C.BLOCK_FORM_SHAPES, C.BLOCK_FORM_SEED, C.BLOCK_FORM_TOL)}
+MAX_SCALE, MAX_SEQ = 100.0, 2049      # as tests/test_hip_sasblock.py: x of a sequence of a second visit of forward launch 1, scaled
+_LIST = {}
+
+
+def _list_case(which, i, p=0.0, peak=False):
+    """(inputs, masks' seed, float64 result) of a case of BLOCK_WALK_SHAPES / BLOCK_FORM_SHAPES, computed once"""
+    key = (which, i, p, peak)
+    if key not in _LIST:
+        shapes, seed, _ = LISTS[which]
+        x, sd, g, heads, lens = C.make_block_case(i, shapes=shapes, seed=seed)
+        assert lens.max() == x.shape[1] and lens.min() == 1
+        if peak:
+            x = x.copy()
+            x[MAX_SEQ] *= MAX_SCALE
+        m1, m2 = C.R.masks_for(SEED + seed + i, *x.shape, p)
+        _LIST[key] = ((x, sd, g, heads, lens), SEED + seed + i, C.block_keys_f64(x, sd, heads, lens, g, m1=m1, m2=m2))
+    return _LIST[key]
+
+
+def _assert_list_figures(which, tag, res, ref):
+    tol = LISTS[which][2]
+    out, gx, gp = res
+    got = {"out": out.cpu().numpy(), "gx": gx.cpu().numpy()}
+    fig = C.figures(got["out"], got["gx"], {n: v.cpu().numpy() for n, v in gp.items()}, ref)
+    print(C.block_fmt("%s %s" % (which, tag), fig, tol))
+    if which == "walk":
+        print("parity sasblock_keys walk %s visits (b < %d | later): %s" % (tag, C.R.BWD_WG,
+                                                                          C.R.visit_fmt(C.R.visit_figures(got, ref, C.R.BWD_WG))))
+    for n, v in fig.items():
+        assert v <= tol[C.group_of(n)], (tag, n, v, tol[C.group_of(n)])
+
+
+@pytest.mark.parametrize("i", range(len(C.BLOCK_WALK_SHAPES)), ids=["x".join(map(str, s)) for s in C.BLOCK_WALK_SHAPES])
+@pytest.mark.parametrize("p", [0.0, 0.1])
+def test_block_walk_parity_with_float64(i, p):
+    """B above kSasBwdWg (and, at B = 2051, above kSasFwdWg): a workgroup meets several sequences, each with its own key length"""
+    (x, sd, g, heads, lens), seed, ref = _list_case("walk", i, p)
+    err = torch.zeros(1, dtype=torch.int32, device=DEV)
+    res = _run_block(x, sd, g, heads, lens, err, p, seed)
+    assert int(err.item()) == 0
+    _assert_list_figures("walk", "B=%d T=%d D=%d h=%d p=%g" % (*C.BLOCK_WALK_SHAPES[i], p), res, ref)
+
+
+@pytest.mark.parametrize("i", range(len(C.BLOCK_FORM_SHAPES)), ids=["x".join(map(str, s)) for s in C.BLOCK_FORM_SHAPES])
+@pytest.mark.parametrize("p", [0.0, 0.1])
+def test_block_form_parity_with_float64(i, p):
+    """T = 24 | 25 at both D, T = 64 at D = 32: every <D, TM> form of the keyed kernels at its border"""
+    (x, sd, g, heads, lens), seed, ref = _list_case("form", i, p)
+    _assert_list_figures("form", "B=%d T=%d D=%d h=%d p=%g" % (*C.BLOCK_FORM_SHAPES[i], p), _run_block(x, sd, g, heads, lens, None, p, seed), ref)
+
+
+def test_block_walk_global_maximum_found_on_a_later_visit():
+    """as tests/test_hip_sasblock.py's: the call's largest score on sequence 2049 of (2051, 2, 64, 4), 10 - 30 above the rest"""
+    i = C.BLOCK_WALK_SHAPES.index((2051, 2, 64, 4))
+    (x, sd, g, heads, lens), seed, ref = _list_case("walk", i, 0.0, True)
+    rest = np.delete(ref["seq_max"], MAX_SEQ).max()
+    assert MAX_SEQ >= C.R.FWD_WG and int(ref["seq_max"].argmax()) == MAX_SEQ and 10.0 < ref["gmax"] - rest < 30.0
+    stored = []
+    res = _run_block(x, sd, g, heads, lens, stored_max=stored)
+    print("parity sasblock_keys walk maximum: stored %.6f float64 %.6f (best of the other sequences %.6f)" % (stored[0], ref["gmax"], rest))
+    assert abs(stored[0] - ref["gmax"]) <= 1e-5 * abs(ref["gmax"])
+    _assert_list_figures("walk", "B=2051 maximum at b=%d" % MAX_SEQ, res, ref)
+
+
+def test_block_walk_two_identical_calls_give_equal_bits():
+    """the shape with the most visits (4 - 5 per workgroup of the backward), p = 0.1"""
+    (x, sd, g, heads, lens), seed, _ = _list_case("walk", C.BLOCK_WALK_SHAPES.index((2051, 2, 64, 4)), 0.1)
+    out, gx, gp = _run_block(x, sd, g, heads, lens, None, 0.1, seed)
+    out2, gx2, gp2 = _run_block(x, sd, g, heads, lens, None, 0.1, seed)
+    assert torch.equal(out, out2) and torch.equal(gx, gx2) and all(torch.equal(gp[n], gp2[n]) for n in gp)
+
+
+def test_block_walk_bad_length_on_a_later_visit_is_clamped_and_reported():
+    """key_len 0 and T + 1 at sequences b >= kSasBwdWg (the second visit of workgroups 1 and 2): the error word is set and the
+    result is the restatement's with the clamped lengths"""
+    i = C.BLOCK_WALK_SHAPES.index((1027, 5, 32, 2))
+    (x, sd, g, heads, lens), _, _ = _list_case("walk", i)
+    T, G = x.shape[1], C.R.BWD_WG
+    bad, good = lens.copy(), lens.copy()
+    bad[G + 1], bad[G + 2] = 0, T + 1
+    good[G + 1], good[G + 2] = 1, T
+    assert (bad[:G] >= 1).all() and (bad[:G] <= T).all()
+    err = torch.zeros(1, dtype=torch.int32, device=DEV)
+    res = _run_block(x, sd, g, heads, bad, err)
+    assert int(err.item()) == 1
+    _assert_list_figures("walk", "B=1027 clamped lengths", res, C.block_keys_f64(x, sd, heads, good, g))
+    res2 = _run_block(x, sd, g, heads, good)
+    assert torch.equal(res[0], res2[0]) and torch.equal(res[1], res2[1]) and all(torch.equal(res[2][n], res2[2][n]) for n in res[2])
 
 
 # ------------------------------------------------------------------------------------------------ the loss

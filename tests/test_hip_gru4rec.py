@@ -71,6 +71,44 @@ def test_two_identical_calls_give_equal_bits(shape, pattern):
         assert _same_bits(a[n], b[n]), n
 
 
+# ------------------------------------------------------------------------------------------------ several tiles per workgroup
+WALK = [(i, pat) for i in range(len(R.WALK_SHAPES)) for pat in R.walk_patterns(i)]
+
+
+def _walk_case(i, pattern):
+    key = ("walk", i, pattern)
+    if key not in _CASES:
+        c = R.make_case(i, pattern, R.WALK_SHAPES, R.WALK_SEED)
+        _CASES[key] = (c, R.case_f64(c))
+    return _CASES[key]
+
+
+@pytest.mark.parametrize("shape,pattern", WALK, ids=["%s-%s" % ("x".join(map(str, R.WALK_SHAPES[i])), pat) for i, pat in WALK])
+def test_walk_parity_with_float64(shape, pattern):
+    """more tiles than kGruBwdWg (and, at B = 16400, than kGruFwdWg): a workgroup takes several tiles, each from h = 0 and with
+    its own lengths, and carries the parameter-gradient partials across them"""
+    c, ref = _walk_case(shape, pattern)
+    B, T, E, H = R.WALK_SHAPES[shape]
+    assert hip_ops.gru_supports(E, H, T)
+    got = _run(c)
+    fig = R.figures(got, ref)
+    print(R.fmt("walk %s %s" % (R.WALK_SHAPES[shape], pattern), fig, R.WALK_TOL))
+    print("parity gru walk %s %s visits (b < %d | later): %s" % (R.WALK_SHAPES[shape], pattern, R.BWD_ROWS,
+                                                               R.visit_fmt(R.visit_figures(got, ref, R.BWD_ROWS))))
+    w = R.worst(fig)
+    for g in R.GROUPS:
+        assert w[g] < R.WALK_TOL[g], (g, w[g], fig)
+    assert not got["gx"][np.arange(T)[None, :] >= c["lengths"][:, None]].any()      # exactly zero past every row's length
+
+
+def test_walk_two_identical_calls_give_equal_bits():
+    """the shape with the most visits: 1,025 tiles, 4 - 5 per workgroup of the backward, 2 for one of the forward"""
+    c, _ = _walk_case(R.WALK_SHAPES.index((16400, 2, 32, 64)), "mixed")
+    a, b = _run(c), _run(c)
+    for n in a:
+        assert _same_bits(a[n], b[n]), n
+
+
 @pytest.mark.parametrize("shape", [2, 3, 4])
 def test_the_padding_is_never_read(shape):
     """NaN at t >= lengths[b]: bitwise the results of zeros there"""

@@ -74,6 +74,47 @@ def test_pool_matches_float64_and_repeats_its_bits(pool_cases, i):
         assert v <= R.TOL, (k, v)
 
 
+# ------------------------------------------------------------------------------------------------ several visits per workgroup
+_WALK = {}
+
+
+def _walk_case(i):
+    if i not in _WALK:
+        c = R.make_case(i, R.WALK_CASES, R.WALK_SEED)
+        _WALK[i] = (c, R.pool_ref(c, g_out=c["g_out"]))
+    return _WALK[i]
+
+
+@pytest.mark.parametrize("i", range(len(R.WALK_CASES)), ids=["x".join(map(str, s)) for s in R.WALK_CASES])
+def test_pool_walk_parity_with_float64(i):
+    """B above kIpBwdWg (and, at B = 4099, above kIpFwdWg): a workgroup meets several sequences, each under its own history mask
+    (a row of length 1 and all-zero rows among the later ones), and carries the partials of the parameter gradients across them"""
+    c, ref = _walk_case(i)
+    got = _pool(c)
+    fig = R.figures(got, ref)
+    print("parity if4rec pool walk case %s: %s (tol %.0e)" % (R.WALK_CASES[i], " ".join("%s=%.2e" % kv for kv in fig.items()), R.WALK_TOL))
+    print("parity if4rec pool walk case %s visits (b < %d | later): %s" % (R.WALK_CASES[i], R.BWD_WG,
+                                                                         R.visit_fmt(R.visit_figures(got, ref, R.BWD_WG))))
+    valid = c["hist"] > 0
+    zero_rows = ~valid.any(axis=1)
+    assert zero_rows[R.BWD_WG:].any() and (valid[R.BWD_WG:].sum(axis=1) == 1).any()
+    for k in got:
+        assert np.isfinite(got[k]).all(), k
+    assert (got["g_hp"][~valid] == 0).all()                                      # exactly zero at masked positions
+    assert (got["out"][zero_rows] == 0).all() and (got["g_hp"][zero_rows] == 0).all()
+    assert (got["g_pos"][c["hist"].shape[1]:] == 0).all()                        # position rows past T
+    for k, v in fig.items():
+        assert v <= R.WALK_TOL, (k, v)
+
+
+def test_pool_walk_two_identical_calls_give_equal_bits():
+    """the case with the most visits: 8 - 9 per workgroup of the backward, 2 for three of the forward"""
+    c, _ = _walk_case(R.WALK_CASES.index((4099, 2, 64, 8, 1)))
+    got, again = _pool(c), _pool(c)
+    for k in got:
+        assert np.array_equal(got[k], again[k]), k
+
+
 def test_pool_without_a_position_table(pool_cases):
     from whisprrec_amd import hip_ops
     c, _ = pool_cases[2]

@@ -72,6 +72,68 @@ def test_two_identical_calls_give_equal_bits(shape, pattern):
         assert np.array_equal(a[n].view(np.int32), b[n].view(np.int32)), n
 
 
+# ------------------------------------------------------------------------------------------------ several visits per workgroup
+def _walk_case(i, pattern):
+    key = ("walk", i, pattern)
+    if key not in _CASES:
+        c = R.make_case(i, pattern, R.WALK_SHAPES, R.WALK_SEED)
+        _CASES[key] = (c, R.case_f64(c))
+    return _CASES[key]
+
+
+def _assert_walk(tag, got, ref):
+    fig = R.figures(got, ref)
+    print(R.fmt("walk %s" % tag, fig, R.WALK_TOL))
+    print("parity ti_attention walk %s visits (b < %d | later): %s" % (tag, R.BWD_WG, R.visit_fmt(R.visit_figures(got, ref, R.BWD_WG))))
+    w = R.worst(fig)
+    for g in R.GROUPS:
+        assert w[g] < R.WALK_TOL[g], (g, w[g], fig)
+
+
+@pytest.mark.parametrize("pattern", R.PATTERNS)
+@pytest.mark.parametrize("shape", range(len(R.WALK_SHAPES)), ids=["x".join(map(str, s)) for s in R.WALK_SHAPES])
+def test_walk_parity_with_float64(shape, pattern):
+    """B above kTiBwdWg (and, at B = 4099, above kTiFwdWg): a workgroup of the backward adds the pairs of several sequences into
+    its slab of the two table gradients"""
+    c, ref = _walk_case(shape, pattern)
+    B, T, D, heads, time_max = R.WALK_SHAPES[shape]
+    assert hip_ops.ti_attention_supports(D, heads, T, time_max)
+    got = _run(c)
+    _assert_walk("%s %s" % (R.WALK_SHAPES[shape], pattern), got, ref)
+    used = np.zeros(time_max + 1, bool)                                   # rows no pair lands on receive exactly nothing
+    used[np.unique(R.intervals(c["times"], c["min_interval"], time_max)[:, np.tril(np.ones((T, T), bool))])] = True
+    assert not got["gtk"][~used].any() and not got["gtv"][~used].any()
+    if pattern == "equal":
+        assert used.sum() == 1 and used[0]
+
+
+def test_walk_two_identical_calls_give_equal_bits():
+    """the shape with the most visits (16 - 17 per workgroup of the backward), every pair on row 0 of the tables"""
+    c, _ = _walk_case(R.WALK_SHAPES.index((4099, 2, 32, 1, 4)), "equal")
+    a, b = _run(c), _run(c)
+    for n in a:
+        assert np.array_equal(a[n].view(np.int32), b[n].view(np.int32)), n
+
+
+def test_walk_bad_min_interval_on_a_later_visit_is_clamped_and_reported():
+    """min_interval 0 and -7 at sequences b >= kTiBwdWg only: the error word is set, the result is that of the scale 1"""
+    shape = R.WALK_SHAPES.index((259, 7, 32, 2, 8))
+    c = dict(_walk_case(shape, "spread")[0])
+    rng = np.random.RandomState(5)
+    c["times"] = 1_000 + np.cumsum(rng.randint(0, 4, c["times"].shape), axis=1)     # gaps of a few units, as in the test below
+    bad = c["min_interval"].copy()
+    bad[[R.BWD_WG, R.BWD_WG + 2]] = [0, -7]
+    assert (bad[:R.BWD_WG] >= 1).all()
+    err = torch.zeros(1, dtype=torch.int32, device=DEV)
+    got = _run(c, err_word=err, min_interval=bad)
+    assert int(err.item()) == 1
+    c["min_interval"] = np.maximum(bad, 1)
+    _assert_walk("clamped scale", got, R.case_f64(c))
+    err.zero_()
+    _run(c, err_word=err)
+    assert int(err.item()) == 0
+
+
 def test_zero_min_interval_sets_the_error_word_and_is_clamped():
     c, _ = _case(1, "spread")
     c = dict(c)

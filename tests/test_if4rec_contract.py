@@ -116,6 +116,72 @@ def test_wrong_pooling_variants_land_above_the_tolerance(cases, refs, wrong):
     assert worst > 10 * R.TOL, (wrong, worst)
 
 
+# ------------------------------------------------------------------------------------------------ several visits per workgroup
+@pytest.fixture(scope="module")
+def walk_cases():
+    cases = [R.make_case(i, R.WALK_CASES, R.WALK_SEED) for i in range(len(R.WALK_CASES))]
+    return [(c, R.pool_ref(c, g_out=c["g_out"])) for c in cases]
+
+
+def _kernel_constant(name):
+    import re
+    import whisprrec_amd
+    with open(os.path.join(os.path.dirname(os.path.abspath(whisprrec_amd.__file__)), "csrc", "wr_if4rec.hip")) as fh:
+        return int(re.search(r"constexpr int %s = (\d+);" % name, fh.read()).group(1))
+
+
+def test_walk_cases_walk_hold_their_rows_and_leave_the_old_cases_alone(cases, walk_cases):
+    assert R.FWD_WG == _kernel_constant("kIpFwdWg") and R.BWD_WG == _kernel_constant("kIpBwdWg")
+    G = R.BWD_WG
+    assert all(B > G and B % G not in (0, G - 1) for B, *_ in R.WALK_CASES)                      # a ragged last visit
+    assert any(B > 2 * G for B, *_ in R.WALK_CASES) and any(B > R.FWD_WG for B, *_ in R.WALK_CASES)
+    assert all(B <= 130 for B, *_ in R.CASES)
+    for (B, T, D, A, K), (c, _) in zip(R.WALK_CASES, walk_cases):
+        n_valid = (c["hist"] > 0).sum(axis=1)
+        assert c["hist"].shape == (B, T) and c["W1"].shape == (A, D) and c["W2"].shape == (K, A)
+        assert n_valid[0] == 1 and n_valid[1] == T and n_valid[B - 1] == 0
+        if T >= 3:
+            assert c["hist"][2, 1] == 0 and c["hist"][2, 0] > 0 and c["hist"][2, 2] > 0            # an interior zero
+        assert n_valid[G + 1] == 1 and (n_valid[G:] == 0).any()                                   # ... and on a later visit
+        assert ((c["hist"] > 0)[G:] != (c["hist"] > 0)[:B - G]).any()
+    c = cases[2]                                                                                 # the draws of an old case, as before
+    rng = np.random.RandomState(1402)
+    assert np.array_equal(c["item"], (rng.standard_normal((R.N_ITEMS, 32)) * 0.5).astype(np.float32))
+
+
+def test_walk_floors_and_tolerance(walk_cases):
+    """WALK_FLOORS = the stock fp32 torch path against float64 over WALK_CASES; WALK_TOL = 8 x the largest, rounded up to one
+    digit; 4 x floor < WALK_TOL"""
+    floors = {k: 0.0 for k in R.FIGURES}
+    for c, _ in walk_cases:
+        c = R.drop_zero_rows(c)
+        ref = R.pool_ref(c, g_out=c["g_out"])
+        fig = R.figures(torch_pool(c, torch.float32), ref)
+        for k, v in fig.items():
+            floors[k] = max(floors[k], v)
+        for k, v in R.figures(torch_pool(c, torch.float64), ref).items():      # and the restatement holds at these sizes
+            assert v <= 1e-12, (k, v)
+    print("if4rec walk floors (fp32 torch vs float64): " + " ".join("%s=%.2e" % kv for kv in floors.items()))
+    top = 8 * max(R.WALK_FLOORS.values())
+    digit = 10.0 ** np.floor(np.log10(top))
+    assert R.WALK_TOL == pytest.approx(np.ceil(top / digit - 1e-9) * digit, rel=1e-9)
+    assert 8 * max(R.WALK_FLOORS.values()) <= R.WALK_TOL <= 16 * max(R.WALK_FLOORS.values())
+    for k, v in floors.items():
+        assert 4 * v < R.WALK_TOL, (k, v)
+
+
+@pytest.mark.parametrize("wrong", R.WALK_WRONG)
+@pytest.mark.parametrize("i", range(len(R.WALK_CASES)))
+def test_walk_mutants_land_five_tolerances_out(walk_cases, i, wrong):
+    """parameter and position gradients of the first visits only; a later visit's out and g_hp, or its history mask, those of the
+    visit before — each exceeds 5 x WALK_TOL on some figure, at every walk case"""
+    c, ref = walk_cases[i]
+    fig = R.figures(R.walk_wrong(c, ref, wrong, R.BWD_WG), ref)
+    print("walk mutant %s at %s: largest figure / tolerance %.1f (%s)" % (wrong, R.WALK_CASES[i], max(fig.values()) / R.WALK_TOL,
+                                                                           max(fig, key=fig.get)))
+    assert max(fig.values()) >= 5.0 * R.WALK_TOL, fig
+
+
 @pytest.mark.parametrize("KQ", [2, 4])
 @pytest.mark.parametrize("wrong", R.WRONG_RANK)
 def test_wrong_rank_variants_change_judged_ranks(wrong, KQ):

@@ -106,6 +106,106 @@ def test_wrong_blocks_land_above_the_tolerances(cases, wrong):
     assert all(v == 0.0 for v in clean.values())
 
 
+# ------------------------------------------------------------------------------------------------ several visits, every form
+LISTS = {"walk": (R.WALK_SHAPES, R.WALK_SEED, R.WALK_FLOORS, R.WALK_TOL), "form": (R.FORM_SHAPES, R.FORM_SEED, R.FORM_FLOORS, R.FORM_TOL)}
+_LIST_REFS = {}
+
+
+def _list_ref(which, i, p):
+    """(inputs, masks, float64 result) of a case of WALK_SHAPES / FORM_SHAPES, computed once"""
+    if (which, i, p) not in _LIST_REFS:
+        shapes, seed = LISTS[which][:2]
+        x, sd, g, heads = R.make_case(i, shapes=shapes, seed=seed)
+        m1, m2 = R.masks_for(SEED + seed + i, *x.shape, p)
+        _LIST_REFS[(which, i, p)] = ((x, sd, g, heads), (m1, m2), R.block_f64(x, sd, heads, g, m1, m2))
+    return _LIST_REFS[(which, i, p)]
+
+
+def _kernel_constant(source, name):
+    import re
+    path = os.path.join(os.path.dirname(os.path.abspath(host.__file__)), "csrc", source)
+    with open(path) as fh:
+        return int(re.search(r"constexpr int %s = (\d+);" % name, fh.read()).group(1))
+
+
+def test_walk_shapes_walk_and_the_new_lists_leave_the_old_cases_alone(g5):
+    """every WALK shape has B above the backward's cap, one above forward launch 1's; the caps restated in sasblock_ref.py are the
+    kernel's; FORM_SHAPES holds T = 24 and T = 25 at both D and a <32, 64> shape; SHAPES' data is what it was"""
+    assert R.FWD_WG == _kernel_constant("wr_sasblock.hip", "kSasFwdWg") and R.BWD_WG == _kernel_constant("wr_sasblock.hip", "kSasBwdWg")
+    assert all(B > R.BWD_WG and B % R.BWD_WG not in (0, R.BWD_WG - 1) for B, _, _, _ in R.WALK_SHAPES)      # a ragged last visit
+    assert any(B > 2 * R.BWD_WG for B, _, _, _ in R.WALK_SHAPES)                                            # a few workgroups visit three
+    assert any(B > R.FWD_WG for B, _, _, _ in R.WALK_SHAPES)
+    assert any(B > R.BWD_WG and D == 32 and T > 24 for B, T, D, _ in R.WALK_SHAPES)
+    assert {(D, T) for _, T, D, _ in R.FORM_SHAPES} >= {(32, 24), (32, 25), (64, 24), (64, 25), (32, 64)}
+    assert all(B <= 130 for B, _, _, _ in R.SHAPES)
+    x, sd, g, heads = R.make_case(2)
+    rng = np.random.RandomState(7002)                                                                    # the draws of case 2, as before
+    R.xavier_params(32, 2, rng)
+    assert np.array_equal(x, (rng.standard_normal((5, 7, 32)) * np.sqrt(2.0 / (3706 + 32)) * np.sqrt(2.0)).astype(np.float32))
+    assert not np.array_equal(R.make_case(2, shapes=R.FORM_SHAPES, seed=R.FORM_SEED)[1]["linear1.bias"], sd["linear1.bias"])
+
+
+@pytest.mark.parametrize("which", ["walk", "form"])
+def test_walk_and_form_tolerances_stand_above_the_fp32_floor_of_the_stock_block(which):
+    shapes, seed, floors, tol = LISTS[which]
+    worst = {k: 0.0 for k in tol}
+    for i in range(len(shapes)):
+        for p in (0.0, 0.1):
+            (x, sd, g, heads), (m1, m2), ref = _list_ref(which, i, p)
+            stock = R.stock_fp32(x, sd, heads, g, m1, m2)
+            fig = R.figures(*stock, ref)
+            print(R.fmt("%s floor B=%d T=%d D=%d h=%d p=%g" % (which, *shapes[i], p), fig, tol))
+            for k, v in R.worst(fig).items():
+                worst[k] = max(worst[k], v)
+            if p == 0.1:                      # the restatement itself, in float64 under autograd
+                f64 = R.figures(*R.stock_fp32(x, sd, heads, g, m1, m2, dtype=torch.float64), ref)
+                assert max(f64.values()) <= 1e-12, f64
+    print("%s floor (largest): " % which + " ".join("%s %.2e" % kv for kv in worst.items()))
+    for k in tol:
+        assert 4.0 * worst[k] < tol[k], (k, worst[k], tol[k])
+        assert 8.0 * floors[k] <= tol[k] <= 16.0 * floors[k] and tol[k] == R.rule_of(floors[k])
+        assert R.rule_of(R.FLOORS[k]) == R.TOL[k]
+
+
+WALK_WRONG = ["later_visits_dropped", "later_visits_stale", "mask_of_first_visit"]
+
+
+@pytest.mark.parametrize("wrong", WALK_WRONG)
+@pytest.mark.parametrize("i", range(len(R.WALK_SHAPES)))
+def test_walk_mutants_land_five_tolerances_out(i, wrong):
+    """parameter gradients summed over each workgroup's first visit only; the output and gx of a later visit those of the visit
+    before; the dropout mask of a later visit taken at the first visit's b — each exceeds 5 x WALK_TOL on some figure, at every
+    walk shape"""
+    (x, sd, g, heads), (m1, m2), ref = _list_ref("walk", i, 0.1)
+    if wrong == "later_visits_dropped":
+        bad = R.block_f64(x, sd, heads, g, m1, m2, wrong=wrong, first=R.BWD_WG)
+    elif wrong == "later_visits_stale":
+        bad = R.stale(ref, R.BWD_WG)
+    else:
+        src = R.first_visit_of(x.shape[0], R.BWD_WG)
+        bad = R.block_f64(x, sd, heads, g, m1[src], m2[src])
+    fig = R.figures(bad["out"], bad["gx"], bad["g"], ref)
+    margin = {n: v / R.WALK_TOL[R.group_of(n)] for n, v in fig.items()}
+    print("walk mutant %s at %s: largest figure / tolerance %.1f (%s)" % (wrong, R.WALK_SHAPES[i], max(margin.values()), max(margin, key=margin.get)))
+    assert max(margin.values()) >= 5.0, margin
+    if wrong == "later_visits_stale":         # and the per-visit figures say which side is wrong
+        first, later = R.visit_figures(bad, ref, R.BWD_WG)["out"]
+        assert first == 0.0 and later == fig["out"]
+
+
+def test_walk_maximum_of_the_first_visits_only_misses_the_stored_maximum():
+    """`max_of_first_visit`: the GPU test's case (x of sequence 2049 of (2051, 2, 64, 4) times 100) — a maximum folded over the
+    first kSasFwdWg sequences misses the call's by far more than 5 x the 1e-5 the stored one is held to"""
+    i = R.WALK_SHAPES.index((2051, 2, 64, 4))
+    x, sd, g, heads = R.make_case(i, shapes=R.WALK_SHAPES, seed=R.WALK_SEED)
+    x = x.copy()
+    x[2049] *= 100.0
+    ref = R.block_f64(x, sd, heads)
+    bad = ref["seq_max"][:R.FWD_WG].max()
+    assert ref["gmax"] == ref["seq_max"].max() and 10.0 < ref["gmax"] - bad < 30.0
+    assert abs(bad - ref["gmax"]) > 5.0 * 1e-5 * abs(ref["gmax"])
+
+
 # ------------------------------------------------------------------------------------------------ the mask generator
 def test_mask_generator_rate_and_streams():
     n = 1 << 20

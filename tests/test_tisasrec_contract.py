@@ -138,6 +138,64 @@ def test_floors_hold(shape, pattern):
         assert 4 * floors[g] < R.TOL[g], (g, floors[g])
 
 
+# ------------------------------------------------------------------------------------------------ several visits per workgroup
+_WALK = {}
+
+
+def _walk(i, pattern):
+    if (i, pattern) not in _WALK:
+        c = R.make_case(i, pattern, R.WALK_SHAPES, R.WALK_SEED)
+        _WALK[(i, pattern)] = (c, R.case_f64(c))
+    return _WALK[(i, pattern)]
+
+
+def _kernel_constant(name):
+    import re
+    import whisprrec_amd
+    with open(os.path.join(os.path.dirname(os.path.abspath(whisprrec_amd.__file__)), "csrc", "wr_tiattn.hip")) as fh:
+        return int(re.search(r"constexpr int %s = (\d+);" % name, fh.read()).group(1))
+
+
+def test_walk_shapes_walk_and_leave_the_old_cases_alone():
+    assert R.FWD_WG == _kernel_constant("kTiFwdWg") and R.BWD_WG == _kernel_constant("kTiBwdWg")
+    assert all(B > R.BWD_WG and B % R.BWD_WG not in (0, R.BWD_WG - 1) for B, *_ in R.WALK_SHAPES)          # a ragged last visit
+    assert any(B > 2 * R.BWD_WG for B, *_ in R.WALK_SHAPES) and any(B > R.FWD_WG for B, *_ in R.WALK_SHAPES)
+    assert all(B <= 130 for B, *_ in R.SHAPES)
+    c = R.make_case(1, "spread")                                            # the draws of an old case, as before
+    rng = np.random.RandomState(9010)
+    assert np.array_equal(c["q"], (rng.standard_normal((5, 7, 32)) * 0.7).astype(np.float32))
+    assert not np.array_equal(R.make_case(0, "spread", R.WALK_SHAPES, R.WALK_SEED)["tk"][:, :4], R.make_case(1, "spread")["tk"][:, :4])
+
+
+def test_walk_tolerances_are_eight_floors():
+    from sasblock_ref import rule_of
+    for g in R.GROUPS:
+        assert 8 * R.WALK_FLOORS[g] <= R.WALK_TOL[g] <= 16 * R.WALK_FLOORS[g] and R.WALK_TOL[g] == rule_of(R.WALK_FLOORS[g]), g
+
+
+@pytest.mark.parametrize("pattern", R.PATTERNS)
+@pytest.mark.parametrize("shape", range(len(R.WALK_SHAPES)), ids=["x".join(map(str, s)) for s in R.WALK_SHAPES])
+def test_walk_floors_hold(shape, pattern):
+    c, ref = _walk(shape, pattern)
+    floors = R.worst(R.figures(R.stock_fp32(c), ref))
+    print("walk floor %s %s: " % (R.WALK_SHAPES[shape], pattern) + " ".join("%s %.2e" % (g, floors[g]) for g in R.GROUPS))
+    for g in R.GROUPS:
+        assert 4 * floors[g] < R.WALK_TOL[g], (g, floors[g])
+
+
+@pytest.mark.parametrize("wrong", ["later_visits_dropped", "later_visits_stale"])
+@pytest.mark.parametrize("pattern", R.PATTERNS)
+@pytest.mark.parametrize("shape", range(len(R.WALK_SHAPES)), ids=["x".join(map(str, s)) for s in R.WALK_SHAPES])
+def test_walk_mutants_land_five_tolerances_out(shape, pattern, wrong):
+    """the table gradients of the first visits only; a later visit's out, gq, gk, gv those of the visit before"""
+    c, ref = _walk(shape, pattern)
+    fig = R.figures(R.walk_wrong(c, ref, wrong, R.BWD_WG), ref)
+    margin = {n: v / R.WALK_TOL[R.GROUP_OF[n]] for n, v in fig.items()}
+    print("walk mutant %s at %s %s: largest figure / tolerance %.1f (%s)" % (wrong, R.WALK_SHAPES[shape], pattern, max(margin.values()),
+                                                                              max(margin, key=margin.get)))
+    assert max(margin.values()) >= 5.0, margin
+
+
 # ------------------------------------------------------------------------------------------------ the two rules
 def test_interval_rule():
     from whisprrec_amd.tisasrec import interval_matrix

@@ -18,7 +18,8 @@ so d time_k is measured absolutely, against the largest sum of the MAGNITUDES of
 
 Tolerances: DESIGN section 2's rule.  The floor of a group is the stock fp32 torch path (ti_attention_torch under autograd, what
 --ti_native 0 runs) against this restatement on a CPU; FLOORS holds the largest floor over SHAPES x PATTERNS; TOL = 8 x that,
-rounded up to one digit.  tests/test_tisasrec_contract.py re-measures the floors and asserts 4 x floor < TOL.
+rounded up to one digit.  tests/test_tisasrec_contract.py re-measures the floors and asserts 4 x floor < TOL.  WALK_SHAPES
+(B above the kernels' workgroup caps: a workgroup visits several sequences) has WALK_FLOORS / WALK_TOL of its own, by the same rule.
 """
 import numpy as np
 
@@ -42,6 +43,23 @@ GROUP_OF = {"out": "out", "gv": "gv", "gtv": "gv", "gq": "gqk", "gk": "gqk", "gt
 # off-diagonal pair of the call.
 FLOORS = {"out": 1.5e-7, "gv": 1.6e-5, "gqk": 1.2e-5, "gtk": 2.5e-7}
 TOL = {"out": 2e-6, "gv": 2e-4, "gqk": 1e-4, "gtk": 2e-6}                  # 8 x floor, rounded up to one digit
+
+# The caps of wr_tiattn.hip restated: a workgroup takes the sequences b, b + cap, b + 2 cap, ... once B exceeds the cap.
+FWD_WG = 4096      # kTiFwdWg: workgroups of the forward
+BWD_WG = 256       # kTiBwdWg: workgroups of the backward = slabs of table-gradient partials, added into on every visit
+
+# Shapes at which a workgroup visits several sequences (backward: 2 - 3 visits, the last one ragged; (4099, 2, 32, 1, 4) walks the
+# forward too, and gives the backward 16 - 17 visits).  Every pattern runs: with "equal" every pair of every visit adds into row 0
+# of the workgroup's slab.
+WALK_SHAPES = [(259, 7, 32, 2, 8), (515, 20, 64, 4, 512), (4099, 2, 32, 1, 4)]
+WALK_SEED = 19000                             # make_case's seed base of this list (SHAPES: 9000)
+# Largest floor of each group over WALK_SHAPES x PATTERNS, measured as FLOORS is (measure_floors(shapes=WALK_SHAPES, seed=WALK_SEED))
+# — the largest seen over three runs (the thread order of torch's CPU gather backward moves gv between 6.4e-6 and 1.04e-5, gtk
+# between 1.2e-7 and 1.4e-7).  out and gv peak at (515, 20, 64, 4, 512) "spread" / "far", gqk at (4099, 2, 32, 1, 4) "spread".
+WALK_FLOORS = {"out": 1.65e-7, "gv": 1.04e-5, "gqk": 5.98e-6, "gtk": 1.41e-7}
+WALK_TOL = {"out": TOL["out"], "gv": 9e-5, "gqk": 5e-5, "gtk": TOL["gtk"]}  # 8 x floor, rounded up to one digit; TOL's where equal
+# The wrong results of a walk (walk_wrong below), smallest largest-figure / WALK_TOL over WALK_SHAPES x PATTERNS: later_visits_dropped
+# 6.4e2 (at (259, 7, 32, 2, 8) "equal": 3 of 259 sequences missing), later_visits_stale 3.5e5.
 
 
 # ------------------------------------------------------------------------------------------------ intervals
@@ -77,10 +95,11 @@ def make_times(pattern, B, T, time_max, rng):
     return 1_000_000_000 + np.cumsum(gaps, axis=1), m
 
 
-def make_case(i, pattern):
-    """-> dict(q, k, v, gout [B, T, D] fp32, tk, tv [time_max + 1, D] fp32, times, min_interval, heads, time_max) of SHAPES[i]"""
-    B, T, D, heads, time_max = SHAPES[i]
-    rng = np.random.RandomState(9000 + 10 * i + PATTERNS.index(pattern))
+def make_case(i, pattern, shapes=None, seed=9000):
+    """-> dict(q, k, v, gout [B, T, D] fp32, tk, tv [time_max + 1, D] fp32, times, min_interval, heads, time_max) of SHAPES[i];
+    shapes / seed: another list (WALK_SHAPES) with its own seed base"""
+    B, T, D, heads, time_max = (SHAPES if shapes is None else shapes)[i]
+    rng = np.random.RandomState(seed + 10 * i + PATTERNS.index(pattern))
     f = lambda *s: rng.standard_normal(s)                   # noqa: E731
     c = {"q": f(B, T, D) * 0.7, "k": f(B, T, D) * 0.7, "v": f(B, T, D) * 0.5, "gout": f(B, T, D),
          "tk": f(time_max + 1, D) * 0.4, "tv": f(time_max + 1, D) * 0.4}
@@ -252,9 +271,59 @@ def worst(fig):
     return w
 
 
-def fmt(tag, fig):
-    w = worst(fig)
-    return "parity ti_attention %s: " % tag + " ".join("%s %.2e (tol %.0e)" % (g, w[g], TOL[g]) for g in GROUPS)
+def fmt(tag, fig, tol=None):
+    w, tol = worst(fig), TOL if tol is None else tol
+    return "parity ti_attention %s: " % tag + " ".join("%s %.2e (tol %.0e)" % (g, w[g], tol[g]) for g in GROUPS)
+
+
+# ------------------------------------------------------------------------------------------------ several visits per workgroup
+PER_SEQUENCE = ("out", "gq", "gk", "gv")
+
+
+def first_sequences(c, n):
+    """the case cut to its first n sequences (the tables stay)"""
+    cut = dict(c)
+    for k in ("q", "k", "v", "gout", "times", "min_interval"):
+        cut[k] = c[k][:n]
+    return cut
+
+
+def first_visit_of(B, cap):
+    """int64 [B]: b for b < cap, b - cap after it — the sequence a workgroup saw one visit earlier"""
+    src = np.arange(B)
+    src[cap:] -= cap
+    return src
+
+
+def visit_figures(got, ref, cap):
+    """{name: (first, later)}: the figure of each per-sequence array apart for the sequences of a workgroup's first visit
+    (b < cap) and of its later ones, both against the whole array's max |ref|"""
+    fig = {}
+    for n in PER_SEQUENCE:
+        a, b = np.asarray(got[n], np.float64), np.asarray(ref[n], np.float64)
+        den = max(float(np.max(np.abs(b))), 1e-300)
+        fig[n] = (float(np.max(np.abs(a[:cap] - b[:cap]))) / den, float(np.max(np.abs(a[cap:] - b[cap:]))) / den if len(b) > cap else 0.0)
+    return fig
+
+
+def visit_fmt(fig):
+    return " ".join("%s first %.2e later %.2e" % (n, *v) for n, v in fig.items())
+
+
+def walk_wrong(c, ref, wrong, cap):
+    """deliberately WRONG results of a walk: 'later_visits_dropped' (the two table gradients summed over the sequences b < cap
+    only), 'later_visits_stale' (out, gq, gk, gv of sequence b >= cap replaced by those of b - cap)"""
+    bad = dict(ref)
+    if wrong == "later_visits_dropped":
+        part = case_f64(first_sequences(c, cap))
+        bad["gtk"], bad["gtv"] = part["gtk"], part["gtv"]
+    elif wrong == "later_visits_stale":
+        src = first_visit_of(len(ref["out"]), cap)
+        for n in PER_SEQUENCE:
+            bad[n] = ref[n][src]
+    else:
+        raise ValueError(wrong)
+    return bad
 
 
 def stock_fp32(c, device="cpu"):
@@ -274,12 +343,14 @@ def stock_fp32(c, device="cpu"):
     return res
 
 
-def measure_floors(shapes=None, patterns=PATTERNS):
-    """-> {group: largest figure of the stock fp32 path against float64 on a CPU}, and the per-case figures"""
+def measure_floors(shapes=None, patterns=PATTERNS, walk=False):
+    """-> {group: largest figure of the stock fp32 path against float64 on a CPU}, and the per-case figures; `shapes`: indices
+    into SHAPES, or into WALK_SHAPES with walk=True"""
     floors, cases = {g: 0.0 for g in GROUPS}, {}
-    for i in (range(len(SHAPES)) if shapes is None else shapes):
+    lst = (WALK_SHAPES, WALK_SEED) if walk else (None, 9000)
+    for i in (range(len(WALK_SHAPES if walk else SHAPES)) if shapes is None else shapes):
         for pat in patterns:
-            c = make_case(i, pat)
+            c = make_case(i, pat, *lst)
             w = worst(figures(stock_fp32(c), case_f64(c)))
             cases[(i, pat)] = w
             for g in GROUPS:
