@@ -719,6 +719,8 @@ int32_t wr_embloss_sumsq(const float *user_tab, const float *item_tab, int32_t D
  *      full_predict (src/models/general/BPRMF.py:82-91), without materialising the [n, n_items] score matrix:
  *   rank[i] = 1 + #{ j not in mask(eval_user[i]) : <user_mat[eval_user[i]], item_tab[j]>  >  target_score[i] }
  *   target_score[i] = <user_mat[eval_user[i]], item_tab[eval_target[i]]>
+ *   A NaN target_score[i] (a diverged model) compares false with every item: such a row gets rank[i] = n_items + 1, behind
+ *   everything, in wr_rank_eval_rows and wr_rank_eval_multi alike.  A NaN score of another item never counts.
  * mask_ptr int64 [n_user_rows+1] / mask_idx int32 (ascending per user): the user's train + dev + test items, which the
  * reference sets to -inf (BaseRunner.py:246-255); both NULL = no masking (--test_all 0).  Scores are computed on the matrix
  * cores with v_mfma_f32_32x32x2_f32 (exact fp32 k-ordered fma chain).  rank: int32 [n]; target_score: fp32 [n] (output).

@@ -108,9 +108,12 @@ __global__ __launch_bounds__(kBlock, 3) void eval_rank_kernel_rega(const float *
     count.flush(rank_cnt);
 }
 
-__global__ __launch_bounds__(kBlock) void eval_finish_kernel(int *__restrict__ rank, int64_t n) {
+// count -> rank.  A NaN target score compares false with every item and would come out of the count as rank 1: such a row
+// ranks behind all n_items items instead, so it is a miss at every k ("Ties and non-finite scores").
+__global__ __launch_bounds__(kBlock) void eval_finish_kernel(int *__restrict__ rank, const float *__restrict__ tscore,
+                                                              int64_t n_items, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i < n) rank[i] += 1;
+    if (i < n) rank[i] = (tscore[i] != tscore[i]) ? (int)(n_items + 1) : rank[i] + 1;
 }
 
 // The launches behind wr_rank_eval and wr_rank_eval_rows; arguments are checked by the entries.
@@ -137,7 +140,8 @@ static int32_t rank_eval_launch(const float *query_mat, const float *item_tab, i
                            target_score, n, mask_ptr, mask_idx, rank);
     }
     WR_LAUNCH_CHECK("eval_rank_kernel");
-    hipLaunchKernelGGL(eval_finish_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, rank, n);
+    hipLaunchKernelGGL(eval_finish_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, rank,
+                       target_score, n_items, n);
     WR_LAUNCH_CHECK("eval_finish_kernel");
     return WR_OK;
 }
@@ -275,7 +279,8 @@ static int32_t rank_eval_multi_launch(const float *query_mat, const float *item_
                            target_score, n, mask_ptr, mask_idx, rank);
     }
     WR_LAUNCH_CHECK("eval_rank_multi_kernel");
-    hipLaunchKernelGGL(eval_finish_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, rank, n);
+    hipLaunchKernelGGL(eval_finish_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, rank,
+                       target_score, n_items, n);
     WR_LAUNCH_CHECK("eval_finish_kernel");
     return WR_OK;
 }

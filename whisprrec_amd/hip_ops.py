@@ -1142,7 +1142,9 @@ def rank_eval_supports(D):
 
 def rank_eval(user_mat, item_tab, eval_user, eval_target, mask_ptr=None, mask_idx=None):
     """Rank of the ground-truth item among all (unmasked) items for every evaluation row (reference
-    BaseRunner.interface + evaluate_method); returns (rank int32 [n], target_score fp32 [n])."""
+    BaseRunner.interface + evaluate_method); returns (rank int32 [n], target_score fp32 [n]).  rank = 1 + the unmasked items
+    scoring strictly above the target; a row whose target score is NaN ranks n_items + 1 (here, in rank_eval_rows and in
+    rank_eval_multi alike)."""
     _req(user_mat, torch.float32, "user_mat", 2)
     _req(item_tab, torch.float32, "item_tab", 2)
     eu, et = _idx64(eval_user.reshape(-1), "eval_user"), _idx64(eval_target.reshape(-1), "eval_target")
