@@ -1298,6 +1298,42 @@ int32_t wr_gru_bwd(const float *x, const int64_t *lengths, const float *w_ih, co
                    float *g_w_ih, float *g_w_hh, float *g_b_ih, float *g_b_hh, void *workspace, int64_t workspace_bytes,
                    void *stream);
 
+/* K27, the whole output sequence (hip_ops.gru_seq: NARM's local encoder, the lower layers of a stacked GRU4Rec).  The same
+ * walk, shapes, refusals and workspace as wr_gru_fwd / _bwd; compile-time variants of the same kernels.
+ *   - wr_gru_seq_fwd: hs [B, T, H] is the result: every step's state for t < len_b and EXACTLY ZERO for t >= len_b
+ *     (pad_packed_sequence's form, not the frozen state wr_gru_fwd stores).  For t < len_b the bits are wr_gru_fwd's.
+ *   - wr_gru_seq_bwd: hs as wr_gru_seq_fwd wrote it; g_hs [B, T, H] enters at every step: g_hs[b, t, :] is added to dh before
+ *     step t's gate gradients, for t < len_b only; g_hs[b, t, :] is never read for t >= len_b.  g_last [B, H] (may be NULL:
+ *     none) is a gradient of the state after step len_b - 1 on top.  Outputs, launches and reproducibility as wr_gru_bwd. */
+int32_t wr_gru_seq_fwd(const float *x, const int64_t *lengths, const float *w_ih, const float *w_hh, const float *b_ih,
+                       const float *b_hh, int64_t B, int32_t T, int32_t E, int32_t H, float *hs, void *stream);
+int32_t wr_gru_seq_bwd(const float *x, const int64_t *lengths, const float *w_ih, const float *w_hh, const float *b_ih,
+                       const float *b_hh, const float *hs, const float *g_hs, const float *g_last, int64_t B, int32_t T, int32_t E,
+                       int32_t H, float *gx, float *g_w_ih, float *g_w_hh, float *g_b_ih, float *g_b_hh, void *workspace,
+                       int64_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * K28 — NARM's additive attention pooling (whisprrec_amd/narm.py, --pool_native 1), forward and backward, fp32.
+ * hs [B, T, H], h_g [B, H], lengths int64 [B], A1, A2 [A, H], v [A]; for row b, len = min(max(lengths[b], 0), T):
+ *   q = A1 h_g[b]     u_t = q + A2 hs[b, t]     e_t = v . sigmoid(u_t)     c[b] = sum_{t < len} e_t hs[b, t]      (no softmax)
+ *   - len = 0 gives c[b] = 0 and no gradient from the row.  hs[b, t, :] is never read for t >= len.
+ *   - Supported (wr_narm_pool_supported): H in {32, 64}, A in {16, 32, 64}, T >= 1, 1 <= B <= 2^24.  Anything else, a NULL or
+ *     misaligned (16 B: hs, A1, A2) pointer or a short workspace is refused (WR_E_*) with the numbers before any launch.
+ *   - wr_narm_pool_fwd: one launch, c [B, H]; A1, A2 and v stay in LDS; nothing is kept for the backward.
+ *   - wr_narm_pool_bwd: g_c [B, H] -> g_hs [B, T, H] (exactly zero for t >= len, every element written), g_h_g [B, H], g_A1,
+ *     g_A2 [A, H], g_v [A], all fully written.  sigmoid(u_t) is recomputed; no [B, T, A] array in memory.  Two launches: each
+ *     wave keeps the parameter gradients of its rows in registers and writes one slab; the second launch folds the slabs in
+ *     (workgroup, wave) order.  No float atomics: same inputs, same bits.
+ *   - workspace >= wr_narm_pool_workspace_bytes(B, T, H, A), 16-byte aligned (backward only): 256 slabs of 2 A H + A floats,
+ *     independent of B and T. */
+int32_t wr_narm_pool_supported(int32_t H, int32_t A, int32_t T);
+int64_t wr_narm_pool_workspace_bytes(int64_t B, int32_t T, int32_t H, int32_t A);
+int32_t wr_narm_pool_fwd(const float *hs, const float *h_g, const int64_t *lengths, const float *A1, const float *A2, const float *v,
+                         int64_t B, int32_t T, int32_t H, int32_t A, float *c, void *stream);
+int32_t wr_narm_pool_bwd(const float *hs, const float *h_g, const int64_t *lengths, const float *A1, const float *A2, const float *v,
+                         const float *g_c, int64_t B, int32_t T, int32_t H, int32_t A, float *g_hs, float *g_h_g, float *g_A1,
+                         float *g_A2, float *g_v, void *workspace, int64_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

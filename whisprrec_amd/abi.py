@@ -259,6 +259,14 @@ SIGNATURES = {
     "wr_gru_fwd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "wr_gru_bwd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp,
                            c_vp, c_i64, c_vp]),
+    "wr_gru_seq_fwd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp]),
+    "wr_gru_seq_bwd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp,
+                               c_vp, c_vp, c_i64, c_vp]),
+    "wr_narm_pool_supported": (c_i32, [c_i32, c_i32, c_i32]),
+    "wr_narm_pool_workspace_bytes": (c_i64, [c_i64, c_i32, c_i32, c_i32]),
+    "wr_narm_pool_fwd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp]),
+    "wr_narm_pool_bwd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                 c_vp, c_i64, c_vp]),
 }
 
 

@@ -23,6 +23,11 @@
 // sums, in registers across all t and all tiles of the workgroup.  Each workgroup writes its accumulators once to its own slab
 // [3H E | 3H H | 3H | 3H] of the workspace; the second launch folds the slabs in workgroup order.  No float atomics; grid, walk
 // and fold order depend on (B, T, E, H) alone: same inputs, same bits.
+//
+// The whole output sequence (wr_gru_seq_fwd / _bwd; NARM's local encoder, the lower layers of a stacked GRU4Rec) is a compile-time
+// variant of both kernels, SEQ: the forward's hs is then the result and zero for t >= len_b; the backward adds g_hs[b, t, :] to dh
+// before step t's gate gradients (t < len_b only, step t - 1's values fetched while step t computes: RPT registers more).  The
+// SEQ = false instantiations hold no trace of it: their instruction streams are the ones from before the variant existed.
 #include <math.h>
 
 #include "wr_common.h"
@@ -125,7 +130,8 @@ __device__ __forceinline__ void gru_gate_sums(const float *Wi, const float *Wh, 
     }
 }
 
-template <int E, int H>
+// SEQ (wr_gru_seq_fwd): hs is the result, zero for t >= len_b (pad_packed_sequence's form), and h_last is not written.
+template <int E, int H, bool SEQ = false>
 __global__ __launch_bounds__(kBlock) void gru_fwd_kernel(GruParams P, float *__restrict__ h_last, float *__restrict__ hs) {
     using S = GruShape<E, H>;
     extern __shared__ float4 gru_lds4[];
@@ -179,21 +185,33 @@ __global__ __launch_bounds__(kBlock) void gru_fwd_kernel(GruParams P, float *__r
 #pragma unroll
                 for (int i = 0; i < S::RPT; ++i) hh[(row0 + i) * H + j] = hreg[i];
             }
-            if (hs != nullptr) {
+            if constexpr (SEQ) {
+#pragma unroll
+                for (int i = 0; i < S::RPT; ++i)
+                    if (b0 + row0 + i < P.B) hs[((b0 + row0 + i) * T + t) * H + j] = t < lr[i] ? hreg[i] : 0.f;
+            } else if (hs != nullptr) {
 #pragma unroll
                 for (int i = 0; i < S::RPT; ++i)
                     if (b0 + row0 + i < P.B) hs[((b0 + row0 + i) * T + t) * H + j] = hreg[i];
             }
         }
+        if constexpr (!SEQ) {
 #pragma unroll
-        for (int i = 0; i < S::RPT; ++i)
-            if (b0 + row0 + i < P.B) h_last[(b0 + row0 + i) * H + j] = hreg[i];
+            for (int i = 0; i < S::RPT; ++i)
+                if (b0 + row0 + i < P.B) h_last[(b0 + row0 + i) * H + j] = hreg[i];
+        }
     }
 }
 
-template <int E, int H>
+// SEQ (wr_gru_seq_bwd): a gradient enters at every step: g_hs[b, t, j] is added to dh before step t's gate gradients, for
+// t < len_b only (the padding of g_hs is never read); step t - 1's values are fetched while step t computes.  g_last may be NULL.
+// hs is then wr_gru_seq_fwd's (zero past the length): the walk reads hs[b, t - 1] for t < len_b alone, so either form serves.
+// g_hs is the last argument, unused and NULL without SEQ: the arguments before it sit where they always did.  (A shared
+// __device__ body behind two __global__ entries was tried: the compiler then schedules the SEQ = false kernels differently.)
+template <int E, int H, bool SEQ = false>
 __global__ __launch_bounds__(kBlock) void gru_bwd_kernel(GruParams P, const float *__restrict__ hs, const float *__restrict__ g_last,
-                                                         float *__restrict__ gx, float *__restrict__ slabs) {
+                                                         float *__restrict__ gx, float *__restrict__ slabs,
+                                                         const float *__restrict__ g_hs) {
     using S = GruShape<E, H>;
     extern __shared__ float4 gru_lds4[];
     float *Wi = reinterpret_cast<float *>(gru_lds4), *Wh = Wi + 3 * H * S::LDI, *xs = Wi + S::W_WORDS, *hp = xs + kGruRows * E;
@@ -222,7 +240,12 @@ __global__ __launch_bounds__(kBlock) void gru_bwd_kernel(GruParams P, const floa
 #pragma unroll
         for (int i = 0; i < S::RPT; ++i) {
             lr[i] = len_s[row0 + i];
-            dh[i] = b0 + row0 + i < P.B ? g_last[(b0 + row0 + i) * H + j] : 0.f;
+            if constexpr (SEQ) {
+                dh[i] = 0.f;
+                if (g_last != nullptr && b0 + row0 + i < P.B) dh[i] = g_last[(b0 + row0 + i) * H + j];
+            } else {
+                dh[i] = b0 + row0 + i < P.B ? g_last[(b0 + row0 + i) * H + j] : 0.f;
+            }
         }
 #pragma unroll
         for (int i = 0; i < S::RPX; ++i) lx[i] = len_s[rowx0 + i];
@@ -238,6 +261,18 @@ __global__ __launch_bounds__(kBlock) void gru_bwd_kernel(GruParams P, const floa
             if (t < xlen) xn = xp[(int64_t)t * (E / 4)];
             if (t < hlen && t > 0) hn = hsp[(int64_t)(t - 1) * (H / 4)];
         }
+        float gn[SEQ ? S::RPT : 1];      // SEQ: g_hs[row][t][j] of the step about to run (rows past their length: 0, unread)
+        const float *ghp = nullptr;
+        (void)gn;
+        (void)ghp;
+        if constexpr (SEQ) {
+            ghp = g_hs + ((b0 + row0) * (int64_t)T) * H + j;      // + (i T + t) H
+#pragma unroll
+            for (int i = 0; i < S::RPT; ++i) {
+                gn[i] = 0.f;
+                if (maxlen > 0 && maxlen - 1 < lr[i]) gn[i] = ghp[((int64_t)i * T + (maxlen - 1)) * H];      // maxlen = 0: no step
+            }
+        }
         for (int t = maxlen - 1; t >= 0; --t) {
             if (tid < S::XV) *reinterpret_cast<float4 *>(xs + xrow * E + 4 * xc) = xn;
             if (tid < S::HV) *reinterpret_cast<float4 *>(hp + hrow * H + 4 * hc) = hn;
@@ -246,6 +281,14 @@ __global__ __launch_bounds__(kBlock) void gru_bwd_kernel(GruParams P, const floa
             hn = zero4;
             if (t >= 1 && t - 1 < xlen) xn = xp[(int64_t)(t - 1) * (E / 4)];
             if (t >= 2 && t - 1 < hlen) hn = hsp[(int64_t)(t - 2) * (H / 4)];
+            if constexpr (SEQ) {
+#pragma unroll
+                for (int i = 0; i < S::RPT; ++i) {
+                    if (t < lr[i]) dh[i] += gn[i];
+                    gn[i] = 0.f;
+                    if (t >= 1 && t - 1 < lr[i]) gn[i] = ghp[((int64_t)i * T + (t - 1)) * H];
+                }
+            }
             {      // the step's gates again, and the four pre-activation gradients
                 float ar[S::RPT], az[S::RPT], ain[S::RPT], ahn[S::RPT];
 #pragma unroll
@@ -460,11 +503,69 @@ int32_t wr_gru_bwd(const float *x, const int64_t *lengths, const float *w_ih, co
         if (lds > 64 * 1024)                                                                                                       \
             WR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(gru_bwd_kernel<E_, H_>),                                     \
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                                     \
-        hipLaunchKernelGGL((gru_bwd_kernel<E_, H_>), dim3(n_wg), dim3(kBlock), lds, stream, P, hs, g_last, gx, slabs);             \
+        hipLaunchKernelGGL((gru_bwd_kernel<E_, H_>), dim3(n_wg), dim3(kBlock), lds, stream, P, hs, g_last, gx, slabs,              \
+                           (const float *)nullptr);                                                                                \
     } while (0)
     WR_GRU_DISPATCH(E, H, WR_GRU_BWD);
 #undef WR_GRU_BWD
     WR_LAUNCH_CHECK("gru_bwd_kernel");
+    const int n_wi = 3 * H * E, n_wh = 3 * H * H, n_b = 3 * H, total = n_wi + n_wh + 2 * n_b;
+    hipLaunchKernelGGL(gru_fold_kernel, dim3((total + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, slabs, n_wg, n_wi, n_wh, n_b,
+                       g_w_ih, g_w_hh, g_b_ih, g_b_hh);
+    WR_LAUNCH_CHECK("gru_fold_kernel");
+    return WR_OK;
+}
+
+int32_t wr_gru_seq_fwd(const float *x, const int64_t *lengths, const float *w_ih, const float *w_hh, const float *b_ih,
+                       const float *b_hh, int64_t B, int32_t T, int32_t E, int32_t H, float *hs, void *stream_) {
+    const char *entry = "wr_gru_seq_fwd";
+    const int32_t rc = gru_check(entry, x, lengths, w_ih, w_hh, b_ih, b_hh, B, T, E, H);
+    if (rc != WR_OK) return rc;
+    WR_REQUIRE(hs != nullptr, WR_E_NULL, "%s: NULL argument", entry);
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    const GruParams P{x, w_ih, w_hh, b_ih, b_hh, lengths, B, T};
+    const size_t lds = (size_t)gru_lds_bytes(E, H, false);
+    const int64_t n_tiles = (B + kGruRows - 1) / kGruRows;
+    const unsigned grid = (unsigned)(n_tiles < kGruFwdWg ? n_tiles : kGruFwdWg);
+#define WR_GRU_SEQ_FWD(E_, H_)                                                                                                     \
+    do {                                                                                                                           \
+        if (lds > 64 * 1024)                                                                                                       \
+            WR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(gru_fwd_kernel<E_, H_, true>),                               \
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                                     \
+        hipLaunchKernelGGL((gru_fwd_kernel<E_, H_, true>), dim3(grid), dim3(kBlock), lds, stream, P, (float *)nullptr, hs);        \
+    } while (0)
+    WR_GRU_DISPATCH(E, H, WR_GRU_SEQ_FWD);
+#undef WR_GRU_SEQ_FWD
+    WR_LAUNCH_CHECK("gru_fwd_kernel (seq)");
+    return WR_OK;
+}
+
+int32_t wr_gru_seq_bwd(const float *x, const int64_t *lengths, const float *w_ih, const float *w_hh, const float *b_ih,
+                       const float *b_hh, const float *hs, const float *g_hs, const float *g_last, int64_t B, int32_t T, int32_t E,
+                       int32_t H, float *gx, float *g_w_ih, float *g_w_hh, float *g_b_ih, float *g_b_hh, void *workspace,
+                       int64_t workspace_bytes, void *stream_) {
+    const char *entry = "wr_gru_seq_bwd";
+    int32_t rc = gru_check(entry, x, lengths, w_ih, w_hh, b_ih, b_hh, B, T, E, H);
+    if (rc != WR_OK) return rc;
+    WR_REQUIRE(hs && g_hs && gx && g_w_ih && g_w_hh && g_b_ih && g_b_hh, WR_E_NULL, "%s: NULL argument", entry);      // g_last may be
+    WR_REQUIRE(aligned16(hs) && aligned16(gx), WR_E_ALIGN, "%s: hs and gx must be 16-byte aligned", entry);
+    if ((rc = check_workspace(entry, workspace, workspace_bytes, wr_gru_workspace_bytes(B, T, E, H))) != WR_OK) return rc;
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    const GruParams P{x, w_ih, w_hh, b_ih, b_hh, lengths, B, T};
+    const size_t lds = (size_t)gru_lds_bytes(E, H, true);
+    float *slabs = reinterpret_cast<float *>(workspace);
+    const int64_t n_tiles = (B + kGruRows - 1) / kGruRows;
+    const int n_wg = (int)(n_tiles < kGruBwdWg ? n_tiles : kGruBwdWg);
+#define WR_GRU_SEQ_BWD(E_, H_)                                                                                                     \
+    do {                                                                                                                           \
+        if (lds > 64 * 1024)                                                                                                       \
+            WR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(gru_bwd_kernel<E_, H_, true>),                               \
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                                     \
+        hipLaunchKernelGGL((gru_bwd_kernel<E_, H_, true>), dim3(n_wg), dim3(kBlock), lds, stream, P, hs, g_last, gx, slabs, g_hs); \
+    } while (0)
+    WR_GRU_DISPATCH(E, H, WR_GRU_SEQ_BWD);
+#undef WR_GRU_SEQ_BWD
+    WR_LAUNCH_CHECK("gru_bwd_kernel (seq)");
     const int n_wi = 3 * H * E, n_wh = 3 * H * H, n_b = 3 * H, total = n_wi + n_wh + 2 * n_b;
     hipLaunchKernelGGL(gru_fold_kernel, dim3((total + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, slabs, n_wg, n_wi, n_wh, n_b,
                        g_w_ih, g_w_hh, g_b_ih, g_b_hh);

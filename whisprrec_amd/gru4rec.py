@@ -20,6 +20,10 @@ Two paths:
                             per-step gate activations.  A length of 0 gives a zero state and no gradient; a length above T acts
                             as T (the stock path would index out of range for either).
 A shape the kernels do not take is logged once and keeps the stock path.  ``--emb_lazy`` as SASRec.
+
+``--num_layers L`` (default 1) stacks L GRUs (``nn.GRU(..., num_layers=L)``, no dropout between them); with L = 1 the module, its
+state_dict keys and every result are those of the one-layer model.  Under --gru_native 1 the layers 0 .. L - 2 run through
+``hip_ops.gru_seq`` (every state, zero past the length) and the last through ``hip_ops.gru_last``.
 """
 import logging
 
@@ -29,6 +33,9 @@ import torch.nn as nn
 from . import hip_ops, host
 from .sasrec import EmbLazyMixin, HipEmbedding, _xavier_normal_all
 from .softmax_loss import SoftmaxLossMixin
+
+
+_GRU_PARAMS = ("weight_ih", "weight_hh", "bias_ih", "bias_hh")
 
 
 def make_gru4rec(sequential_model_cls):
@@ -41,6 +48,7 @@ def make_gru4rec(sequential_model_cls):
         def parse_model_args(parser):
             parser.add_argument("--emb_size", type=int, default=64, help="Size of embedding vectors.")
             parser.add_argument("--hidden_size", type=int, default=64, help="Size of hidden vectors in GRU.")
+            parser.add_argument("--num_layers", type=int, default=1, help="Number of stacked GRU layers.")
             parser.add_argument("--gru_native", type=int, default=0, choices=[0, 1],
                                 help="1: the GRU recurrence by the fused HIP kernels (forward and backward), rows stop at their "
                                      "own length; 0: nn.GRU over the padded batch + autograd.")
@@ -52,7 +60,10 @@ def make_gru4rec(sequential_model_cls):
             super().__init__(args, corpus)
             self.emb_size, self.hidden_size, self.max_his = int(args.emb_size), int(args.hidden_size), args.history_max
             self.item_embedding = HipEmbedding(self.item_num, self.emb_size, padding_idx=0)
-            self.rnn = nn.GRU(input_size=self.emb_size, hidden_size=self.hidden_size, batch_first=True)
+            self.num_layers = int(getattr(args, "num_layers", 1))
+            if self.num_layers < 1:
+                raise ValueError("--num_layers must be at least 1 (got %d)" % self.num_layers)
+            self.rnn = nn.GRU(input_size=self.emb_size, hidden_size=self.hidden_size, num_layers=self.num_layers, batch_first=True)
             self.out = nn.Linear(self.hidden_size, self.emb_size)
             self.apply(_xavier_normal_all)      # embeddings and linears; the GRU keeps nn.GRU's own initialisation
             self.gru_native = bool(int(getattr(args, "gru_native", 0)))
@@ -64,7 +75,8 @@ def make_gru4rec(sequential_model_cls):
             if not self.gru_native:
                 return False
             if T not in self._gru_native_ok:
-                ok = hip_ops.gru_supports(self.emb_size, self.hidden_size, T)
+                ok = hip_ops.gru_supports(self.emb_size, self.hidden_size, T) and (
+                    self.num_layers == 1 or hip_ops.gru_supports(self.hidden_size, self.hidden_size, T))
                 if not ok and not any(v is False for v in self._gru_native_ok.values()):
                     logging.warning("--gru_native 1: the GRU kernels do not take emb_size=%d hidden_size=%d history=%d; keeping "
                                     "the torch path", self.emb_size, self.hidden_size, T)
@@ -76,8 +88,9 @@ def make_gru4rec(sequential_model_cls):
             bsz, T = history.shape
             x = self.item_embedding(history)
             if self._use_gru_native(T):
-                h_last = hip_ops.gru_last(x, lengths, self.rnn.weight_ih_l0, self.rnn.weight_hh_l0, self.rnn.bias_ih_l0,
-                                          self.rnn.bias_hh_l0)
+                for layer in range(self.num_layers - 1):      # the lower layers hand every state up
+                    x = hip_ops.gru_seq(x, lengths, *(getattr(self.rnn, "%s_l%d" % (n, layer)) for n in _GRU_PARAMS))
+                h_last = hip_ops.gru_last(x, lengths, *(getattr(self.rnn, "%s_l%d" % (n, self.num_layers - 1)) for n in _GRU_PARAMS))
             else:
                 output, _ = self.rnn(x)
                 h_last = output[torch.arange(bsz, device=history.device), lengths - 1, :]

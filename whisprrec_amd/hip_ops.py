@@ -2109,6 +2109,136 @@ def gru_last(x, lengths, w_ih, w_hh, b_ih, b_hh):
     return _GruLast.apply(x, w_ih, w_hh, b_ih, b_hh, lengths, save_hs)
 
 
+def gru_seq_fwd(x, lengths, w_ih, w_hh, b_ih, b_hh):
+    """The same GRU walk in one launch of wr_gru_seq_fwd -> hs [B, T, H], every step's state: row b's first clamp(lengths[b], 0,
+    T) steps and EXACTLY ZERO after them (pad_packed_sequence's form; gru_fwd(save_hs=True) stores the frozen state there).
+    x[b, t, :] is never read at t >= lengths[b].  For t < lengths[b] the bits are gru_fwd's."""
+    B, T, E, H = _gru_args(x, lengths, w_ih, w_hh, b_ih, b_hh)
+    hs = torch.empty((B, T, H), dtype=torch.float32, device=x.device)
+    abi.check(abi.lib().wr_gru_seq_fwd(_p(x), _p(lengths), _p(w_ih), _p(w_hh), _p(b_ih), _p(b_hh), B, T, E, H, _p(hs), _stream()),
+              "wr_gru_seq_fwd")
+    return hs
+
+
+def gru_seq_bwd(x, lengths, w_ih, w_hh, b_ih, b_hh, hs, g_hs, g_last=None):
+    """The gradients of gru_seq_fwd's hs for g_hs [B, T, H], which enters at every step t < lengths[b] (its padding is never
+    read), and optionally g_last [B, H] on the state after step lengths[b] - 1 (wr_gru_seq_bwd, two launches):
+    (gx [B, T, E], g_w_ih, g_w_hh, g_b_ih, g_b_hh).  gx is exactly zero at t >= lengths[b].  Same inputs, same bits."""
+    B, T, E, H = _gru_args(x, lengths, w_ih, w_hh, b_ih, b_hh)
+    _req(hs, torch.float32, "hs", 3)
+    _req(g_hs, torch.float32, "g_hs", 3)
+    if g_last is not None:
+        _req(g_last, torch.float32, "g_last", 2)
+    if tuple(hs.shape) != (B, T, H) or tuple(g_hs.shape) != (B, T, H) or (g_last is not None and tuple(g_last.shape) != (B, H)):
+        raise ValueError("hs and g_hs must be [B, T, H] = %s and g_last [B, H] or None (got %s, %s and %s)"
+                         % ((B, T, H), tuple(hs.shape), tuple(g_hs.shape), None if g_last is None else tuple(g_last.shape)))
+    gx = torch.empty_like(x)
+    g_w_ih, g_w_hh, g_b_ih, g_b_hh = (torch.empty_like(t) for t in (w_ih, w_hh, b_ih, b_hh))
+    ws = workspace(x.device, "gru").get(gru_workspace_bytes(B, T, E, H))
+    abi.check(abi.lib().wr_gru_seq_bwd(_p(x), _p(lengths), _p(w_ih), _p(w_hh), _p(b_ih), _p(b_hh), _p(hs), _p(g_hs), _p(g_last), B,
+                                       T, E, H, _p(gx), _p(g_w_ih), _p(g_w_hh), _p(g_b_ih), _p(g_b_hh), _p(ws), ws.numel(),
+                                       _stream()), "wr_gru_seq_bwd")
+    return gx, g_w_ih, g_w_hh, g_b_ih, g_b_hh
+
+
+class _GruSeq(torch.autograd.Function):
+    """wr_gru_seq_fwd / _bwd: saves the inputs and its own result hs"""
+
+    @staticmethod
+    def forward(ctx, x, w_ih, w_hh, b_ih, b_hh, lengths):
+        args = [t.detach().contiguous() for t in (x, w_ih, w_hh, b_ih, b_hh)]
+        hs = gru_seq_fwd(args[0], lengths, *args[1:])
+        ctx.save_for_backward(lengths, hs, *args)
+        return hs
+
+    @staticmethod
+    def backward(ctx, g_hs):
+        lengths, hs, x, w_ih, w_hh, b_ih, b_hh = ctx.saved_tensors
+        gx, g_w_ih, g_w_hh, g_b_ih, g_b_hh = gru_seq_bwd(x, lengths, w_ih, w_hh, b_ih, b_hh, hs, g_hs.contiguous())
+        return gx, g_w_ih, g_w_hh, g_b_ih, g_b_hh, None
+
+
+def gru_seq(x, lengths, w_ih, w_hh, b_ih, b_hh):
+    """gru_seq_fwd under autograd: hs [B, T, H], zero past each row's length, whose backward hands back the kernel's gx and the
+    four parameter gradients for a gradient at every step."""
+    return _GruSeq.apply(x, w_ih, w_hh, b_ih, b_hh, _idx64(lengths, "lengths"))
+
+
+# --------------------------------------------------------------------------------------------------------------- NARM pooling (K28)
+def narm_pool_supports(H, A, T):
+    """shapes wr_narm_pool_fwd / _bwd take (wr_narm_pool_supported): H in {32, 64}, A in {16, 32, 64}, T >= 1"""
+    return bool(abi.lib().wr_narm_pool_supported(int(H), int(A), int(T)))
+
+
+def narm_pool_workspace_bytes(B, T, H, A):
+    return abi.check_size(abi.lib().wr_narm_pool_workspace_bytes(int(B), int(T), int(H), int(A)), "wr_narm_pool_workspace_bytes")
+
+
+def _narm_args(hs, h_g, lengths, A1, A2, v):
+    """the argument checks of narm_pool_fwd / _bwd -> (B, T, H, A)"""
+    _req(hs, torch.float32, "hs", 3)
+    _req(h_g, torch.float32, "h_g", 2)
+    _req(lengths, torch.int64, "lengths", 1)
+    _req(A1, torch.float32, "A1", 2)
+    _req(A2, torch.float32, "A2", 2)
+    _req(v, torch.float32, "v", 1)
+    B, T, H = (int(s) for s in hs.shape)
+    A = int(A1.shape[0])
+    if tuple(h_g.shape) != (B, H) or lengths.numel() != B or tuple(A1.shape) != (A, H) or tuple(A2.shape) != (A, H) or v.numel() != A:
+        raise ValueError("hs must be [B, T, H], h_g [B, H], lengths [B], A1 and A2 [A, H], v [A] (got %s, %s, %s, %s, %s, %s)"
+                         % tuple(tuple(t.shape) for t in (hs, h_g, lengths, A1, A2, v)))
+    if B < 1 or not narm_pool_supports(H, A, T):
+        raise abi.WhisprRecHipError("narm_pool does not support B=%d T=%d H=%d A=%d (H in {32, 64}, A in {16, 32, 64}, T >= 1, "
+                                    "B >= 1)" % (B, T, H, A))
+    return B, T, H, A
+
+
+def narm_pool_fwd(hs, h_g, lengths, A1, A2, v):
+    """NARM's attention pooling in one launch of wr_narm_pool_fwd -> c [B, H]: c[b] = sum_{t < len_b} e_t hs[b, t] with
+    e_t = v . sigmoid(A1 h_g[b] + A2 hs[b, t]) and len_b = clamp(lengths[b], 0, T); hs[b, t, :] is never read at t >= len_b."""
+    B, T, H, A = _narm_args(hs, h_g, lengths, A1, A2, v)
+    c = torch.empty((B, H), dtype=torch.float32, device=hs.device)
+    abi.check(abi.lib().wr_narm_pool_fwd(_p(hs), _p(h_g), _p(lengths), _p(A1), _p(A2), _p(v), B, T, H, A, _p(c), _stream()),
+              "wr_narm_pool_fwd")
+    return c
+
+
+def narm_pool_bwd(hs, h_g, lengths, A1, A2, v, g_c):
+    """The gradients of narm_pool_fwd's c for g_c [B, H] (wr_narm_pool_bwd, two launches; sigmoid(u_t) is recomputed):
+    (g_hs [B, T, H], g_h_g [B, H], g_A1, g_A2 [A, H], g_v [A]).  g_hs is exactly zero at t >= lengths[b].  Same inputs, same bits."""
+    B, T, H, A = _narm_args(hs, h_g, lengths, A1, A2, v)
+    _req(g_c, torch.float32, "g_c", 2)
+    if tuple(g_c.shape) != (B, H):
+        raise ValueError("g_c must be [B, H] = %s (got %s)" % ((B, H), tuple(g_c.shape)))
+    g_hs, g_h_g = torch.empty_like(hs), torch.empty_like(h_g)
+    g_A1, g_A2, g_v = (torch.empty_like(t) for t in (A1, A2, v))
+    ws = workspace(hs.device, "narm").get(narm_pool_workspace_bytes(B, T, H, A))
+    abi.check(abi.lib().wr_narm_pool_bwd(_p(hs), _p(h_g), _p(lengths), _p(A1), _p(A2), _p(v), _p(g_c), B, T, H, A, _p(g_hs),
+                                         _p(g_h_g), _p(g_A1), _p(g_A2), _p(g_v), _p(ws), ws.numel(), _stream()), "wr_narm_pool_bwd")
+    return g_hs, g_h_g, g_A1, g_A2, g_v
+
+
+class _NarmPool(torch.autograd.Function):
+    """wr_narm_pool_fwd / _bwd: saves nothing but the inputs"""
+
+    @staticmethod
+    def forward(ctx, hs, h_g, A1, A2, v, lengths):
+        args = [t.detach().contiguous() for t in (hs, h_g, A1, A2, v)]
+        c = narm_pool_fwd(args[0], args[1], lengths, *args[2:])
+        ctx.save_for_backward(lengths, *args)
+        return c
+
+    @staticmethod
+    def backward(ctx, g_c):
+        lengths, hs, h_g, A1, A2, v = ctx.saved_tensors
+        return narm_pool_bwd(hs, h_g, lengths, A1, A2, v, g_c.contiguous()) + (None,)
+
+
+def narm_pool(hs, h_g, lengths, A1, A2, v):
+    """narm_pool_fwd under autograd: c [B, H] whose backward hands back the kernel's gradients of hs, h_g, A1, A2 and v."""
+    return _NarmPool.apply(hs, h_g, A1, A2, v.reshape(-1), _idx64(lengths, "lengths"))
+
+
 def sgd_dense(tab, grad, lr, l2=0.0, stamp=None, step_id=0):
     abi.check(abi.lib().wr_sgd_dense(_p(_req(tab, torch.float32, "tab", 2)), tab.shape[0], tab.shape[1],
                                      _p(_req(grad, torch.float32, "grad", 2)), _p(stamp), step_id, lr, l2, _stream()),

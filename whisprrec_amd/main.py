@@ -19,11 +19,11 @@ import sys
 import numpy as np
 import torch
 
-from . import bprmf, buir, contrarec, gru4rec, if4rec, lightgcn, reader, runner, sasrec, sgl, tisasrec
+from . import bprmf, buir, contrarec, gru4rec, if4rec, lightgcn, narm, reader, runner, sasrec, sgl, tisasrec
 
 MODELS = {"BPRMF": bprmf.BPRMF, "LightGCN": lightgcn.LightGCN, "SGL": sgl.SGL, "SASRec": sasrec.SASRec,
           "ContraRec": contrarec.ContraRec, "BUIR": buir.BUIR, "IF4Rec": if4rec.IF4Rec, "TiSASRec": tisasrec.TiSASRec,
-          "GRU4Rec": gru4rec.GRU4Rec}
+          "GRU4Rec": gru4rec.GRU4Rec, "NARM": narm.NARM}
 READERS = {"BaseReader": reader.BaseReader, "SeqReader": reader.SeqReader}
 RUNNERS = {"BaseRunner": runner.BaseRunner, "HipRunner": runner.HipRunner}
 
